@@ -154,8 +154,8 @@ class BenchTimerCallback(Callback):
     """Times exactly ``steps`` training steps after ``warmup`` untimed
     ones: barrier + cuda.synchronize brackets, MAX over ranks, peak GPU
     memory over the timed region. Stops training when done and leaves
-    ``bench_elapsed_s`` / ``bench_peak_mem_mib`` in callback_metrics
-    (which the launcher ships back to the driver)."""
+    ``bench_elapsed_s`` / ``bench_peak_mem_mib`` / ``bench_last_loss``
+    in callback_metrics (which the launcher ships back to the driver)."""
 
     def __init__(self, warmup: int, steps: int):
         self.warmup = warmup
@@ -186,4 +186,9 @@ class BenchTimerCallback(Callback):
         trainer.strategy.reduce(peak, op="max")
         trainer.callback_metrics["bench_elapsed_s"] = t[0].float()
         trainer.callback_metrics["bench_peak_mem_mib"] = peak[0].float()
+        # after the clock stopped: the last timed step's loss, for
+        # ``bench.py --dump-outputs``
+        loss = outputs["loss"] if isinstance(outputs, dict) else outputs
+        trainer.callback_metrics["bench_last_loss"] = \
+            loss.detach().float().cpu()
         trainer.should_stop = True

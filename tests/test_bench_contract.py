@@ -66,12 +66,69 @@ def test_bench_external_mode_torchrun():
     assert j["config"]["parallelism"] == "dp2"
 
 
-def test_bench_engine_mode():
+def test_bench_dump_outputs_actor_mode(tmp_path):
+    """--dump-outputs writes the last timed step's loss and the sampled
+    model as float32 .npy, and the same arguments give the same inputs
+    (seeded init + data): two runs agree output for output."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        j = _run([BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1",
+                  "--batch-size", "4", "--image-size", "32",
+                  "--num-classes", "10", "--dump-outputs", str(d)])
+        assert j["steps"] == 2 and j["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["loss.npy", "state.npy", "state_names.txt",
+                         "state_offsets.npy"]
+        loss, state = np.load(d / "loss.npy"), np.load(d / "state.npy")
+        assert loss.dtype == np.float32 and loss.shape == (1,)
+        assert state.dtype == np.float32 and state.ndim == 1
+        assert np.isfinite(loss).all() and np.isfinite(state).all()
+        offsets = np.load(d / "state_offsets.npy")
+        names = (d / "state_names.txt").read_text().split()
+        assert len(offsets) == len(names) > 100  # ResNet-50 tensors
+        assert offsets[-1] < state.size
+        total = sum(p.stat().st_size for p in d.iterdir())
+        assert total <= 64 * 1024 * 1024
+        dumps.append((loss, state))
+    # CPU fp32/bf16 kernels are deterministic at these shapes
+    np.testing.assert_array_equal(dumps[0][0], dumps[1][0])
+    np.testing.assert_array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_seed_miopen_find_db(tmp_path, monkeypatch):
+    """The recorded MIOpen find-db is copied into an empty user db
+    directory and never replaces a db that is already there."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    src = os.path.join(REPO, "ray_lightning_amd", "ops", "miopen_db")
+    names = [n for n in os.listdir(src) if n.endswith(".ufdb.txt")]
+    assert names
+    dst = tmp_path / "userdb"
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", str(dst))
+    bench.seed_miopen_find_db()
+    assert sorted(p.name for p in dst.iterdir()) == sorted(names)
+    for n in names:
+        assert (dst / n).read_bytes() == \
+            open(os.path.join(src, n), "rb").read()
+    (dst / names[0]).write_text("mine\n")
+    bench.seed_miopen_find_db()
+    assert (dst / names[0]).read_text() == "mine\n"
+
+
+def test_bench_engine_mode(tmp_path):
     j = _run([BENCH, "--launch", "engine", "--gpus", "1", "--steps",
               "2", "--warmup", "1", "--batch-size", "4",
-              "--image-size", "64", "--num-classes", "10"])
+              "--image-size", "64", "--num-classes", "10", "--full",
+              "--dump-outputs", str(tmp_path)])
     _check_contract(j, 1)
     assert j["config"]["launch"] == "engine"
+    import numpy as np
+    assert np.isfinite(np.load(tmp_path / "loss.npy")).all()
+    assert np.load(tmp_path / "state.npy").dtype == np.float32
 
 
 def test_bench_gpt2_sharded_labels():
