@@ -97,8 +97,9 @@ class ShardedOptimizer(torch.optim.Optimizer):
 
         super().__init__([{"params": self._all_params,
                            **optimizer.defaults}], optimizer.defaults)
-        # expose the inner groups for LR schedulers / clipping on owned
-        # params
+        # expose the inner groups for LR schedulers. They hold only this
+        # rank's shard, so a norm taken over them is a per-shard norm:
+        # global-norm clipping goes through clip_grad_norm() below.
         self.param_groups = self.optim.param_groups
 
     def _seal_bucket(self, rank: int, params: List[nn.Parameter]) -> None:
@@ -115,6 +116,37 @@ class ShardedOptimizer(torch.optim.Optimizer):
         loss = self.optim.step(closure)
         self._broadcast_params()
         return loss
+
+    @torch.no_grad()
+    def clip_grad_norm(self, max_norm: float,
+                       defer: bool = True) -> torch.Tensor:
+        """Clip to the L2 norm of the WHOLE model's gradient and return
+        that norm (FairScale OSS ``clip_grad_norm``). Call it after
+        ``ShardedDDP.finalize_backward``: each rank then holds exactly
+        the reduced grads of the shard it owns, so the global sum of
+        squares is the all-reduced sum of the per-rank ones.
+
+        Every rank issues the all-reduce exactly once per call — a rank
+        that owns no gradient contributes zero — so the collective order
+        never diverges. The coefficient stays on the device; an inner
+        optimizer with ``set_grad_scale`` folds it into its next step,
+        otherwise (or with ``defer=False``, e.g. under a GradScaler that
+        inspects the grads itself) the owned grads are scaled in place.
+        """
+        from .. import ops
+        grads = [p.grad for g in self.optim.param_groups
+                 for p in g["params"] if p.grad is not None]
+        device = (grads[0].device if grads else
+                  self._all_params[0].device if self._all_params else None)
+        sumsq = ops.grad_sumsq(grads, device=device)
+        if self.world_size > 1:
+            self.comm.all_reduce_(sumsq, op="sum")
+        norm, coef = ops.clip_coef(sumsq, max_norm)
+        if defer and hasattr(self.optim, "set_grad_scale"):
+            self.optim.set_grad_scale(coef)
+        else:
+            ops.scale_grads_(grads, coef)
+        return norm.reshape(())
 
     def _broadcast_params(self) -> None:
         if self.world_size <= 1:

@@ -11,6 +11,9 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
 - bucket unpack + 1/world scale (optional bf16->fp32 cast), fused
 - fused SGD(momentum) and Adam/AdamW optimizer steps (multi-tensor)
 - sharded fused Adam (bf16 params/grads, fp32 master state)
+- global-norm clipping: multi-tensor sum of squares (deterministic, no
+  atomics), in-place scale by a device scalar, and an optional gradient
+  multiplier inside the fused optimizer kernels
 """
 from __future__ import annotations
 
@@ -66,6 +69,84 @@ def pack_grads(slots: List[torch.Tensor], grads: List[torch.Tensor]) -> None:
     else:
         for s, g in zip(slots, flat_grads):
             s.copy_(g)
+
+
+def _flat_view(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """1-D alias of a dense tensor's memory (element order is irrelevant
+    to a norm or a scale), or None when the layout has no such view.
+    Covers contiguous and channels_last grads."""
+    if t.is_contiguous():
+        return t.view(-1)
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        return t.permute(0, 2, 3, 1).reshape(-1)
+    if t.dim() == 5 and t.is_contiguous(
+            memory_format=torch.channels_last_3d):
+        return t.permute(0, 2, 3, 4, 1).reshape(-1)
+    return None
+
+
+def _kernel_dtypes(tensors: List[torch.Tensor]) -> bool:
+    """The clip kernels cover the dtypes this project trains in (fp32,
+    bf16). Gradients of any other dtype (fp16, fp64) are not a missing
+    kernel but outside the kernels' contract: they take the torch math
+    below, as they did before the kernels existed."""
+    return all(t.dtype in (torch.float32, torch.bfloat16) for t in tensors)
+
+
+def _wide(t: torch.Tensor) -> torch.dtype:
+    """fp32, or the tensor's own dtype where that is wider (fp64)."""
+    return torch.promote_types(t.dtype, torch.float32)
+
+
+def grad_sumsq(tensors: List[torch.Tensor],
+               device: Optional[torch.device] = None) -> torch.Tensor:
+    """Sum of squares over a list of fp32/bf16 tensors, accumulated in
+    fp32, as a 1-element fp32 tensor on the tensors' device (``device``
+    only matters for an empty list). Never reads back to the host."""
+    if not tensors:
+        return torch.zeros(1, dtype=torch.float32, device=device)
+    if tensors[0].is_cuda and _kernel_dtypes(tensors):
+        ext = _require_ext()
+        if ext is not None:
+            flat = [_flat_view(t) for t in tensors]
+            return ext.grad_sumsq(
+                [t.reshape(-1) if f is None else f
+                 for t, f in zip(tensors, flat)])
+    # same order as the kernel: per-tensor squares summed in fp32
+    per = [t.to(_wide(t)).pow(2).sum().float() for t in tensors]
+    return torch.stack(per).sum().reshape(1)
+
+
+def clip_coef(sumsq: torch.Tensor, max_norm: float):
+    """``(norm, coef)`` from a sum of squares, by the definition
+    ``torch.nn.utils.clip_grad_norm_`` uses (``error_if_nonfinite=False``):
+    ``coef = min(1, max_norm / (norm + 1e-6))``; a non-finite norm
+    propagates the same way. 1-element device ops, no host read."""
+    norm = sumsq.sqrt()
+    coef = torch.clamp(float(max_norm) / (norm + 1e-6), max=1.0)
+    return norm, coef
+
+
+def scale_grads_(tensors: List[torch.Tensor], coef: torch.Tensor) -> None:
+    """In place ``g *= coef`` for every tensor, ``coef`` a 1-element
+    tensor that stays on the device."""
+    if not tensors:
+        return
+    if tensors[0].is_cuda and _kernel_dtypes(tensors):
+        ext = _require_ext()
+        if ext is not None:
+            coef = coef.to(torch.float32).reshape(1)
+            flat = [_flat_view(t) for t in tensors]
+            ext.multi_tensor_scale([f for f in flat if f is not None],
+                                   coef)
+            for t, f in zip(tensors, flat):
+                if f is None:  # exotic strides: no flat alias exists
+                    t.mul_(coef)
+            return
+    for t in tensors:
+        # multiply in fp32 and round once, like the kernel
+        w = _wide(t)
+        t.copy_((t.to(w) * coef.to(device=t.device, dtype=w)).to(t.dtype))
 
 
 def unpack_scale(bucket, scale: float) -> None:

@@ -10,6 +10,9 @@
 //  - bucket scale / scale+cast (the 1/world_size unflatten step, fused)
 //  - fused SGD(momentum) and Adam/AdamW multi-tensor optimizer steps
 //  - sharded Adam step with bf16 params + fp32 master state
+//  - global-norm clipping: deterministic multi-tensor sum of squares,
+//    in-place scale by a device scalar, and an optional gradient
+//    multiplier inside the three optimizer kernels
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -271,7 +274,304 @@ void scale_cast(torch::Tensor dst, torch::Tensor src, double s) {
 }
 
 // ---------------------------------------------------------------------
+// global-norm gradient clipping: multi-tensor sum of squares and
+// in-place scale by a device scalar. Segments are flat fp32 or bf16
+// tensors, mixed freely in one launch (the dtype branch is uniform per
+// block). A segment's base pointer may be any element-aligned address
+// (a view at an odd offset): the `head` elements before the first
+// 16-byte boundary are handled scalar by the segment's first block and
+// the vector body starts at the boundary, so no 16-byte access is ever
+// misaligned.
+// ---------------------------------------------------------------------
+struct FlatMeta {
+  void* ptr[kMaxSeg];
+  long numel[kMaxSeg];
+  long start_block[kMaxSeg + 1];
+  unsigned char head[kMaxSeg];  // scalar elements before the 16B boundary
+  unsigned char bf16[kMaxSeg];  // 1: __hip_bfloat16, 0: float
+  int n;
+};
+
+// Fixed-order block sum: shuffle-down tree inside each wave64, one LDS
+// word per wave, then a 4-term serial sum. Valid in thread 0 only.
+__device__ __forceinline__ float block_sum(float v, float* lds) {
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// Sum of squares of one 16-byte vector, as a balanced tree so the
+// sequential fp32 chain per thread stays at UNROLL adds.
+template <typename T>
+__device__ __forceinline__ float vec_sumsq(const int4& raw) {
+  constexpr int V = 16 / sizeof(T);
+  T e[V];
+  *reinterpret_cast<int4*>(e) = raw;
+  float sq[V];
+  #pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const float x = ToFloat<T>::conv(e[i]);
+    sq[i] = x * x;
+  }
+  #pragma unroll
+  for (int w = V / 2; w > 0; w >>= 1) {
+    #pragma unroll
+    for (int i = 0; i < w; ++i) sq[i] += sq[i + w];
+  }
+  return sq[0];
+}
+
+template <typename T, int UNROLL>
+__device__ __forceinline__ float seg_sumsq(const T* __restrict__ src,
+                                           long numel, int head,
+                                           long local_block) {
+  constexpr int V = 16 / sizeof(T);
+  const T* __restrict__ body = src + head;
+  const long body_n = numel - head;
+  float acc = 0.f;
+  if (local_block == 0 && (int)threadIdx.x < head) {
+    const float x = ToFloat<T>::conv(src[threadIdx.x]);
+    acc = x * x;
+  }
+  const long block_elems = (long)kThreads * V * UNROLL;
+  const long base = local_block * block_elems;
+  if (base + block_elems <= body_n) {
+    // full block: issue every load before the first use
+    int4 raw[UNROLL];
+    #pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+      raw[u] = *reinterpret_cast<const int4*>(
+          body + base + ((long)u * kThreads + threadIdx.x) * V);
+    #pragma unroll
+    for (int u = 0; u < UNROLL; ++u) acc += vec_sumsq<T>(raw[u]);
+  } else {
+    #pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const long idx = base + ((long)u * kThreads + threadIdx.x) * V;
+      if (idx + V <= body_n) {
+        acc += vec_sumsq<T>(*reinterpret_cast<const int4*>(body + idx));
+      } else {
+        float t = 0.f;
+        for (long i = idx; i < body_n; ++i) {
+          const float x = ToFloat<T>::conv(body[i]);
+          t += x * x;
+        }
+        acc += t;
+      }
+    }
+  }
+  return acc;
+}
+
+template <int UNROLL = 8>
+__global__ __launch_bounds__(kThreads) void multi_tensor_sumsq_kernel(
+    FlatMeta meta, float* __restrict__ partials) {
+  __shared__ float lds[kThreads / 64];
+  int seg = 0;
+  long b = blockIdx.x;
+  while (seg + 1 < meta.n && b >= meta.start_block[seg + 1]) seg++;
+  const long local_block = b - meta.start_block[seg];
+  float acc;
+  if (meta.bf16[seg])
+    acc = seg_sumsq<__hip_bfloat16, UNROLL>(
+        reinterpret_cast<const __hip_bfloat16*>(meta.ptr[seg]),
+        meta.numel[seg], meta.head[seg], local_block);
+  else
+    acc = seg_sumsq<float, UNROLL>(
+        reinterpret_cast<const float*>(meta.ptr[seg]), meta.numel[seg],
+        meta.head[seg], local_block);
+  const float s = block_sum(acc, lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// One level of the partials tree: block i sums in[i*4096 .. +4096) in a
+// fixed order (16 strided terms per thread, then block_sum).
+static constexpr int kFoldPerThread = 16;
+static constexpr long kFoldPerBlock = (long)kThreads * kFoldPerThread;
+
+__global__ __launch_bounds__(kThreads) void sumsq_fold_kernel(
+    const float* __restrict__ in, long n, float* __restrict__ out) {
+  __shared__ float lds[kThreads / 64];
+  const long base = (long)blockIdx.x * kFoldPerBlock;
+  float acc = 0.f;
+  #pragma unroll
+  for (int k = 0; k < kFoldPerThread; ++k) {
+    const long i = base + (long)k * kThreads + threadIdx.x;
+    if (i < n) acc += in[i];
+  }
+  const float s = block_sum(acc, lds);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+// Fill FlatMeta launch by launch; `fn(meta, blocks)` launches one batch.
+template <typename Fn>
+static void for_each_flat_batch(const std::vector<torch::Tensor>& ts,
+                                int unroll, Fn fn) {
+  size_t i = 0;
+  while (i < ts.size()) {
+    FlatMeta meta;
+    int n = 0;
+    long blocks = 0;
+    while (i < ts.size() && n < kMaxSeg) {
+      const torch::Tensor& t = ts[i++];
+      const long numel = t.numel();
+      if (numel == 0) continue;
+      const long es = t.element_size();
+      const long block_elems = (long)kThreads * (16 / es) * unroll;
+      const uintptr_t addr = reinterpret_cast<uintptr_t>(t.data_ptr());
+      TORCH_CHECK(addr % es == 0, "tensor is not element-aligned");
+      const long head = std::min<long>(numel, ((16 - addr % 16) % 16) / es);
+      meta.ptr[n] = t.data_ptr();
+      meta.numel[n] = numel;
+      meta.head[n] = (unsigned char)head;
+      meta.bf16[n] = t.scalar_type() == at::kBFloat16;
+      meta.start_block[n] = blocks;
+      blocks += std::max<long>(
+          1, (numel - head + block_elems - 1) / block_elems);
+      ++n;
+    }
+    meta.start_block[n] = blocks;
+    meta.n = n;
+    if (n > 0) fn(meta, blocks);
+  }
+}
+
+static void check_flat_list(const std::vector<torch::Tensor>& ts,
+                            const char* what) {
+  for (const auto& t : ts) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous(), what,
+                ": tensors must be contiguous GPU tensors");
+    TORCH_CHECK(t.scalar_type() == at::kFloat ||
+                t.scalar_type() == at::kBFloat16,
+                what, ": only fp32 and bf16 are supported");
+    TORCH_CHECK(t.device() == ts[0].device(), what,
+                ": tensors must share one device");
+  }
+}
+
+// sum over all tensors of sum(x^2), fp32, as a 1-element device tensor.
+// Bitwise reproducible: no atomics, every partial has a fixed slot and
+// every level of the tree a fixed order.
+torch::Tensor grad_sumsq(std::vector<torch::Tensor> tensors) {
+  TORCH_CHECK(!tensors.empty(), "grad_sumsq: empty tensor list");
+  check_flat_list(tensors, "grad_sumsq");
+  constexpr int UNROLL = 8;
+  auto opts = tensors[0].options().dtype(at::kFloat);
+  long total = 0;
+  for_each_flat_batch(tensors, UNROLL,
+                      [&](const FlatMeta&, long blocks) { total += blocks; });
+  if (total == 0) return torch::zeros({1}, opts);
+
+  // partials of every level live back to back in one buffer
+  long buf = 0;
+  for (long n = total; n > 1; n = (n + kFoldPerBlock - 1) / kFoldPerBlock)
+    buf += n;
+  auto scratch = torch::empty({buf + 1}, opts);
+  auto out = torch::empty({1}, opts);
+  float* level = scratch.data_ptr<float>();
+
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  long done = 0;
+  for_each_flat_batch(tensors, UNROLL, [&](const FlatMeta& meta,
+                                           long blocks) {
+    hipLaunchKernelGGL((multi_tensor_sumsq_kernel<UNROLL>), dim3(blocks),
+                       dim3(kThreads), 0, stream, meta, level + done);
+    CHECK_HIP(hipGetLastError());
+    done += blocks;
+  });
+  long n = total;
+  for (;;) {
+    const long nb = (n + kFoldPerBlock - 1) / kFoldPerBlock;
+    float* dst = nb == 1 ? out.data_ptr<float>() : level + n;
+    hipLaunchKernelGGL(sumsq_fold_kernel, dim3(nb), dim3(kThreads), 0,
+                       stream, level, n, dst);
+    CHECK_HIP(hipGetLastError());
+    if (nb == 1) break;
+    level += n;
+    n = nb;
+  }
+  return out;
+}
+
+template <typename T, int UNROLL>
+__device__ __forceinline__ void seg_scale(T* __restrict__ p, long numel,
+                                          int head, long local_block,
+                                          float s) {
+  constexpr int V = 16 / sizeof(T);
+  T* __restrict__ body = p + head;
+  const long body_n = numel - head;
+  if (local_block == 0 && (int)threadIdx.x < head)
+    p[threadIdx.x] =
+        FromFloat<T>::conv(ToFloat<T>::conv(p[threadIdx.x]) * s);
+  const long base = local_block * ((long)kThreads * V * UNROLL);
+  #pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    const long idx = base + ((long)u * kThreads + threadIdx.x) * V;
+    if (idx + V <= body_n) {
+      T e[V];
+      *reinterpret_cast<int4*>(e) = *reinterpret_cast<int4*>(body + idx);
+      #pragma unroll
+      for (int i = 0; i < V; ++i)
+        e[i] = FromFloat<T>::conv(ToFloat<T>::conv(e[i]) * s);
+      *reinterpret_cast<int4*>(body + idx) = *reinterpret_cast<int4*>(e);
+    } else {
+      for (long i = idx; i < body_n; ++i)
+        body[i] = FromFloat<T>::conv(ToFloat<T>::conv(body[i]) * s);
+    }
+  }
+}
+
+template <int UNROLL = 4>
+__global__ __launch_bounds__(kThreads) void multi_tensor_scale_kernel(
+    FlatMeta meta, const float* __restrict__ coef) {
+  const float s = *coef;
+  if (s == 1.f) return;  // uniform: nothing to clip, leave grads as is
+  int seg = 0;
+  long b = blockIdx.x;
+  while (seg + 1 < meta.n && b >= meta.start_block[seg + 1]) seg++;
+  const long local_block = b - meta.start_block[seg];
+  if (meta.bf16[seg])
+    seg_scale<__hip_bfloat16, UNROLL>(
+        reinterpret_cast<__hip_bfloat16*>(meta.ptr[seg]), meta.numel[seg],
+        meta.head[seg], local_block, s);
+  else
+    seg_scale<float, UNROLL>(reinterpret_cast<float*>(meta.ptr[seg]),
+                             meta.numel[seg], meta.head[seg], local_block,
+                             s);
+}
+
+static const float* scalar_ptr(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+              t.numel() == 1,
+              what, " must be a 1-element fp32 GPU tensor");
+  return t.data_ptr<float>();
+}
+
+// g *= *coef for every tensor; coef stays on the device.
+void multi_tensor_scale(std::vector<torch::Tensor> tensors,
+                        torch::Tensor coef) {
+  if (tensors.empty()) return;
+  check_flat_list(tensors, "multi_tensor_scale");
+  const float* c = scalar_ptr(coef, "multi_tensor_scale: coef");
+  constexpr int UNROLL = 4;
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  for_each_flat_batch(tensors, UNROLL, [&](const FlatMeta& meta,
+                                           long blocks) {
+    hipLaunchKernelGGL((multi_tensor_scale_kernel<UNROLL>), dim3(blocks),
+                       dim3(kThreads), 0, stream, meta, c);
+    CHECK_HIP(hipGetLastError());
+  });
+}
+
+// ---------------------------------------------------------------------
 // fused multi-tensor SGD (momentum)  — fp32 params/grads/momentum
+//
+// The fused optimizers take an optional device scalar `grad_scale` (the
+// clip coefficient): SCALED kernels multiply every gradient element by
+// it right after conversion to fp32, before weight decay and the
+// moments. The unscaled instantiation is the original math.
 // ---------------------------------------------------------------------
 struct SgdMeta {
   float* p[kMaxSeg];
@@ -282,10 +582,13 @@ struct SgdMeta {
   int n;
 };
 
-template <int UNROLL = 4>
+template <int UNROLL = 4, bool SCALED = false>
 __global__ __launch_bounds__(kThreads) void fused_sgd_kernel(
     SgdMeta meta, float lr, float momentum, float dampening,
-    float weight_decay, int nesterov, int first_step) {
+    float weight_decay, int nesterov, int first_step,
+    const float* __restrict__ grad_scale) {
+  float gs = 1.f;
+  if constexpr (SCALED) gs = *grad_scale;
   int seg = 0;
   long b = blockIdx.x;
   while (seg + 1 < meta.n && b >= meta.start_block[seg + 1]) seg++;
@@ -310,6 +613,7 @@ __global__ __launch_bounds__(kThreads) void fused_sgd_kernel(
       float me[4] = {mv.x, mv.y, mv.z, mv.w};
       #pragma unroll
       for (int i = 0; i < 4; ++i) {
+        if constexpr (SCALED) ge[i] *= gs;
         float d = ge[i] + weight_decay * pe[i];
         if (momentum != 0.f) {
           me[i] = first_step ? d
@@ -325,7 +629,9 @@ __global__ __launch_bounds__(kThreads) void fused_sgd_kernel(
             float4{me[0], me[1], me[2], me[3]};
     } else {
       for (long i = idx; i < numel && i < idx + 4; ++i) {
-        float d = g[i] + weight_decay * p[i];
+        float gi = g[i];
+        if constexpr (SCALED) gi *= gs;
+        float d = gi + weight_decay * p[i];
         if (momentum != 0.f) {
           float mi = first_step ? d
                                 : momentum * m[i] + (1.f - dampening) * d;
@@ -342,8 +648,11 @@ void fused_sgd(std::vector<torch::Tensor> params,
                std::vector<torch::Tensor> grads,
                std::vector<torch::Tensor> momenta, double lr,
                double momentum, double dampening, double weight_decay,
-               bool nesterov, bool first_step) {
+               bool nesterov, bool first_step,
+               c10::optional<torch::Tensor> grad_scale) {
   if (params.empty()) return;
+  const float* gs = grad_scale.has_value()
+      ? scalar_ptr(*grad_scale, "fused_sgd: grad_scale") : nullptr;
   auto stream = at::hip::getCurrentHIPStream().stream();
   constexpr int UNROLL = 4;
   const long block_elems = (long)kThreads * 4 * UNROLL;
@@ -364,11 +673,18 @@ void fused_sgd(std::vector<torch::Tensor> params,
     }
     meta.start_block[n] = blocks;
     meta.n = n;
-    hipLaunchKernelGGL((fused_sgd_kernel<UNROLL>), dim3(blocks),
-                       dim3(kThreads), 0, stream, meta, (float)lr,
-                       (float)momentum, (float)dampening,
-                       (float)weight_decay, (int)nesterov,
-                       (int)first_step);
+    if (gs)
+      hipLaunchKernelGGL((fused_sgd_kernel<UNROLL, true>), dim3(blocks),
+                         dim3(kThreads), 0, stream, meta, (float)lr,
+                         (float)momentum, (float)dampening,
+                         (float)weight_decay, (int)nesterov,
+                         (int)first_step, gs);
+    else
+      hipLaunchKernelGGL((fused_sgd_kernel<UNROLL, false>), dim3(blocks),
+                         dim3(kThreads), 0, stream, meta, (float)lr,
+                         (float)momentum, (float)dampening,
+                         (float)weight_decay, (int)nesterov,
+                         (int)first_step, gs);
     CHECK_HIP(hipGetLastError());
   }
 }
@@ -386,10 +702,13 @@ struct AdamMeta {
   int n;
 };
 
-template <int UNROLL = 4>
+template <int UNROLL = 4, bool SCALED = false>
 __global__ __launch_bounds__(kThreads) void fused_adam_kernel(
     AdamMeta meta, float lr, float beta1, float beta2, float eps,
-    float weight_decay, float bc1, float bc2, int adamw) {
+    float weight_decay, float bc1, float bc2, int adamw,
+    const float* __restrict__ grad_scale) {
+  float gs = 1.f;
+  if constexpr (SCALED) gs = *grad_scale;
   int seg = 0;
   long b = blockIdx.x;
   while (seg + 1 < meta.n && b >= meta.start_block[seg + 1]) seg++;
@@ -420,6 +739,7 @@ __global__ __launch_bounds__(kThreads) void fused_adam_kernel(
       #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float gi = ge[i];
+        if constexpr (SCALED) gi *= gs;
         if (adamw) pe[i] *= (1.f - lr * weight_decay);
         else gi += weight_decay * pe[i];
         me[i] = beta1 * me[i] + (1.f - beta1) * gi;
@@ -437,6 +757,7 @@ __global__ __launch_bounds__(kThreads) void fused_adam_kernel(
     } else {
       for (long i = idx; i < numel && i < idx + 4; ++i) {
         float gi = g[i];
+        if constexpr (SCALED) gi *= gs;
         if (adamw) p[i] *= (1.f - lr * weight_decay);
         else gi += weight_decay * p[i];
         m[i] = beta1 * m[i] + (1.f - beta1) * gi;
@@ -453,8 +774,11 @@ void fused_adam(std::vector<torch::Tensor> params,
                 std::vector<torch::Tensor> exp_avgs,
                 std::vector<torch::Tensor> exp_avg_sqs, double lr,
                 double beta1, double beta2, double eps,
-                double weight_decay, long step, bool adamw) {
+                double weight_decay, long step, bool adamw,
+                c10::optional<torch::Tensor> grad_scale) {
   if (params.empty()) return;
+  const float* gs = grad_scale.has_value()
+      ? scalar_ptr(*grad_scale, "fused_adam: grad_scale") : nullptr;
   auto stream = at::hip::getCurrentHIPStream().stream();
   const float bc1 = 1.f - powf((float)beta1, (float)step);
   const float bc2 = 1.f - powf((float)beta2, (float)step);
@@ -477,10 +801,16 @@ void fused_adam(std::vector<torch::Tensor> params,
     }
     meta.start_block[n] = blocks;
     meta.n = n;
-    hipLaunchKernelGGL((fused_adam_kernel<UNROLL>), dim3(blocks),
-                       dim3(kThreads), 0, stream, meta, (float)lr,
-                       (float)beta1, (float)beta2, (float)eps,
-                       (float)weight_decay, bc1, bc2, (int)adamw);
+    if (gs)
+      hipLaunchKernelGGL((fused_adam_kernel<UNROLL, true>), dim3(blocks),
+                         dim3(kThreads), 0, stream, meta, (float)lr,
+                         (float)beta1, (float)beta2, (float)eps,
+                         (float)weight_decay, bc1, bc2, (int)adamw, gs);
+    else
+      hipLaunchKernelGGL((fused_adam_kernel<UNROLL, false>), dim3(blocks),
+                         dim3(kThreads), 0, stream, meta, (float)lr,
+                         (float)beta1, (float)beta2, (float)eps,
+                         (float)weight_decay, bc1, bc2, (int)adamw, gs);
     CHECK_HIP(hipGetLastError());
   }
 }
@@ -501,10 +831,13 @@ struct ShardedAdamMeta {
   int n;
 };
 
-template <typename GradT, int UNROLL = 4>
+template <typename GradT, int UNROLL = 4, bool SCALED = false>
 __global__ __launch_bounds__(kThreads) void sharded_adam_kernel(
     ShardedAdamMeta meta, float lr, float beta1, float beta2, float eps,
-    float weight_decay, float bc1, float bc2, int adamw) {
+    float weight_decay, float bc1, float bc2, int adamw,
+    const float* __restrict__ grad_scale) {
+  float gs = 1.f;
+  if constexpr (SCALED) gs = *grad_scale;
   int seg = 0;
   long b = blockIdx.x;
   while (seg + 1 < meta.n && b >= meta.start_block[seg + 1]) seg++;
@@ -545,6 +878,7 @@ __global__ __launch_bounds__(kThreads) void sharded_adam_kernel(
       #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float gi = ToFloat<GradT>::conv(gv[i]);
+        if constexpr (SCALED) gi *= gs;
         if (adamw) pe[i] *= (1.f - lr * weight_decay);
         else gi += weight_decay * pe[i];
         me[i] = beta1 * me[i] + (1.f - beta1) * gi;
@@ -564,6 +898,7 @@ __global__ __launch_bounds__(kThreads) void sharded_adam_kernel(
     } else {
       for (long i = idx; i < numel && i < idx + 4; ++i) {
         float gi = ToFloat<GradT>::conv(g[i]);
+        if constexpr (SCALED) gi *= gs;
         float pi = master[i];
         if (adamw) pi *= (1.f - lr * weight_decay);
         else gi += weight_decay * pi;
@@ -584,8 +919,11 @@ void sharded_adam(std::vector<torch::Tensor> params_bf16,
                   std::vector<torch::Tensor> exp_avgs,
                   std::vector<torch::Tensor> exp_avg_sqs, double lr,
                   double beta1, double beta2, double eps,
-                  double weight_decay, long step, bool adamw) {
+                  double weight_decay, long step, bool adamw,
+                  c10::optional<torch::Tensor> grad_scale) {
   if (params_bf16.empty()) return;
+  const float* gs = grad_scale.has_value()
+      ? scalar_ptr(*grad_scale, "sharded_adam: grad_scale") : nullptr;
   auto stream = at::hip::getCurrentHIPStream().stream();
   const float bc1 = 1.f - powf((float)beta1, (float)step);
   const float bc2 = 1.f - powf((float)beta2, (float)step);
@@ -611,18 +949,17 @@ void sharded_adam(std::vector<torch::Tensor> params_bf16,
     }
     meta.start_block[n] = blocks;
     meta.n = n;
-    if (grad_bf16)
-      hipLaunchKernelGGL((sharded_adam_kernel<__hip_bfloat16, UNROLL>),
-                         dim3(blocks), dim3(kThreads), 0, stream, meta,
-                         (float)lr, (float)beta1, (float)beta2,
-                         (float)eps, (float)weight_decay, bc1, bc2,
-                         (int)adamw);
-    else
-      hipLaunchKernelGGL((sharded_adam_kernel<float, UNROLL>),
-                         dim3(blocks), dim3(kThreads), 0, stream, meta,
-                         (float)lr, (float)beta1, (float)beta2,
-                         (float)eps, (float)weight_decay, bc1, bc2,
-                         (int)adamw);
+#define LAUNCH_SHARDED_ADAM(GradT, SCALED)                               \
+    hipLaunchKernelGGL((sharded_adam_kernel<GradT, UNROLL, SCALED>),     \
+                       dim3(blocks), dim3(kThreads), 0, stream, meta,    \
+                       (float)lr, (float)beta1, (float)beta2,            \
+                       (float)eps, (float)weight_decay, bc1, bc2,        \
+                       (int)adamw, gs)
+    if (grad_bf16 && gs) LAUNCH_SHARDED_ADAM(__hip_bfloat16, true);
+    else if (grad_bf16) LAUNCH_SHARDED_ADAM(__hip_bfloat16, false);
+    else if (gs) LAUNCH_SHARDED_ADAM(float, true);
+    else LAUNCH_SHARDED_ADAM(float, false);
+#undef LAUNCH_SHARDED_ADAM
     CHECK_HIP(hipGetLastError());
   }
 }
@@ -807,8 +1144,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dz = dh * gelu_tanh'(z) + column-sum bias grad, one pass");
   m.def("scale_inplace", &scale_inplace, "flat *= s");
   m.def("scale_cast", &scale_cast, "dst_f32 = src_bf16 * s");
-  m.def("fused_sgd", &fused_sgd, "fused multi-tensor SGD(momentum)");
-  m.def("fused_adam", &fused_adam, "fused multi-tensor Adam/AdamW");
+  namespace py = pybind11;
+  // grad_scale is optional and last, so positional calls without it
+  // keep working
+  m.def("fused_sgd", &fused_sgd, "fused multi-tensor SGD(momentum)",
+        py::arg("params"), py::arg("grads"), py::arg("momenta"),
+        py::arg("lr"), py::arg("momentum"), py::arg("dampening"),
+        py::arg("weight_decay"), py::arg("nesterov"),
+        py::arg("first_step"), py::arg("grad_scale") = py::none());
+  m.def("fused_adam", &fused_adam, "fused multi-tensor Adam/AdamW",
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("step"), py::arg("adamw"),
+        py::arg("grad_scale") = py::none());
   m.def("sharded_adam", &sharded_adam,
-        "sharded Adam: bf16 param + fp32 master");
+        "sharded Adam: bf16 param + fp32 master",
+        py::arg("params_bf16"), py::arg("masters"), py::arg("grads"),
+        py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("weight_decay"), py::arg("step"), py::arg("adamw"),
+        py::arg("grad_scale") = py::none());
+  m.def("grad_sumsq", &grad_sumsq,
+        "multi-tensor sum of squares -> 1-element fp32 tensor");
+  m.def("multi_tensor_scale", &multi_tensor_scale,
+        "g *= *coef for a list of tensors, coef on the device");
 }

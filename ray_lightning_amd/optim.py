@@ -23,7 +23,41 @@ def _use_ext(params: List[torch.Tensor]) -> bool:
     return bool(params) and params[0].is_cuda and ops.hip_ext_available()
 
 
-class FusedSGD(Optimizer):
+class _GradScaleMixin:
+    """Deferred gradient multiplier (the clip coefficient): a 1-element
+    tensor that the next ``step()`` folds into the gradient as it streams
+    through the update, then clears, so a stale coefficient can never
+    leak into a later step."""
+
+    _grad_scale: Optional[torch.Tensor] = None
+
+    def set_grad_scale(self, coef: Optional[torch.Tensor]) -> None:
+        self._grad_scale = coef
+
+    def _take_grad_scale(self) -> Optional[torch.Tensor]:
+        coef, self._grad_scale = self._grad_scale, None
+        return coef
+
+
+def _ext_scale(coef: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if coef is None:
+        return None
+    return coef.to(torch.float32).reshape(1)
+
+
+def _scaled(grads: List[torch.Tensor], coef: Optional[torch.Tensor],
+            keep_fp32: bool = False) -> List[torch.Tensor]:
+    """Eager twin of the kernels' ``gi = conv(g) * s``: multiply in fp32.
+    ``keep_fp32`` leaves the product in fp32 (the bf16 sharded path, whose
+    math is fp32 from there on); otherwise it goes back to the grad's own
+    dtype, which for fp32 grads is the same thing."""
+    if coef is None:
+        return grads
+    out = [g.float() * coef.to(g.device) for g in grads]
+    return out if keep_fp32 else [o.to(g.dtype) for o, g in zip(out, grads)]
+
+
+class FusedSGD(_GradScaleMixin, Optimizer):
     def __init__(self, params, lr: float, momentum: float = 0.0,
                  dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False):
@@ -34,6 +68,7 @@ class FusedSGD(Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        coef = self._take_grad_scale()
         for group in self.param_groups:
             params, grads, momenta = [], [], []
             first_step = False
@@ -57,10 +92,11 @@ class FusedSGD(Optimizer):
                 ops._load_ext().fused_sgd(
                     flat_params, grads, momenta, group["lr"],
                     group["momentum"], group["dampening"],
-                    group["weight_decay"], group["nesterov"], first_step)
+                    group["weight_decay"], group["nesterov"], first_step,
+                    _ext_scale(coef))
             else:
-                self._eager_step(flat_params, grads, momenta, group,
-                                 first_step)
+                self._eager_step(flat_params, _scaled(grads, coef),
+                                 momenta, group, first_step)
         return loss
 
     @staticmethod
@@ -83,7 +119,7 @@ class FusedSGD(Optimizer):
         torch._foreach_add_(params, grads, alpha=-lr)
 
 
-class FusedAdamW(Optimizer):
+class FusedAdamW(_GradScaleMixin, Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 1e-2,
                  adamw: bool = True):
@@ -94,6 +130,7 @@ class FusedAdamW(Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        coef = self._take_grad_scale()
         for group in self.param_groups:
             params, grads, avgs, sqs = [], [], [], []
             step_t = 0
@@ -120,9 +157,10 @@ class FusedAdamW(Optimizer):
                 ops._load_ext().fused_adam(
                     params, grads, avgs, sqs, group["lr"], b1, b2,
                     group["eps"], group["weight_decay"], step_t,
-                    group["adamw"])
+                    group["adamw"], _ext_scale(coef))
             else:
-                self._eager_step(params, grads, avgs, sqs, group, step_t)
+                self._eager_step(params, _scaled(grads, coef), avgs, sqs,
+                                 group, step_t)
         return loss
 
     @staticmethod
@@ -146,7 +184,7 @@ class FusedAdamW(Optimizer):
         torch._foreach_add_(params, steps, alpha=-lr / bc1)
 
 
-class ShardedFusedAdam(Optimizer):
+class ShardedFusedAdam(_GradScaleMixin, Optimizer):
     """Adam(W) for bf16 models: bf16 params are mirrored by an fp32
     master copy; the fused kernel updates master state and writes back
     bf16 — the optimizer the sharded strategy pairs with the GPT-2-XL
@@ -162,6 +200,7 @@ class ShardedFusedAdam(Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        coef = self._take_grad_scale()
         for group in self.param_groups:
             p16, masters, grads, avgs, sqs = [], [], [], [], []
             f32_params, f32_grads, f32_avgs, f32_sqs = [], [], [], []
@@ -199,18 +238,21 @@ class ShardedFusedAdam(Optimizer):
                     ops._load_ext().sharded_adam(
                         p16, masters, grads, avgs, sqs, group["lr"], b1,
                         b2, group["eps"], group["weight_decay"], step_t,
-                        group["adamw"])
+                        group["adamw"], _ext_scale(coef))
                 else:
-                    self._eager_bf16(p16, masters, grads, avgs, sqs,
-                                     group, step_t)
+                    self._eager_bf16(p16, masters,
+                                     _scaled(grads, coef, keep_fp32=True),
+                                     avgs, sqs, group, step_t)
             if f32_params:
                 if _use_ext(f32_params):
                     ops._load_ext().fused_adam(
                         f32_params, f32_grads, f32_avgs, f32_sqs,
                         group["lr"], b1, b2, group["eps"],
-                        group["weight_decay"], step_t, group["adamw"])
+                        group["weight_decay"], step_t, group["adamw"],
+                        _ext_scale(coef))
                 else:
-                    FusedAdamW._eager_step(f32_params, f32_grads,
+                    FusedAdamW._eager_step(f32_params,
+                                           _scaled(f32_grads, coef),
                                            f32_avgs, f32_sqs, group,
                                            step_t)
         return loss

@@ -68,6 +68,7 @@ class Trainer:
                  check_val_every_n_epoch: int = 1,
                  accumulate_grad_batches: int = 1,
                  gradient_clip_val: Optional[float] = None,
+                 gradient_clip_algorithm: str = "norm",
                  log_every_n_steps: int = 50,
                  enable_checkpointing: bool = True,
                  enable_progress_bar: bool = False,
@@ -104,6 +105,14 @@ class Trainer:
         self.check_val_every_n_epoch = check_val_every_n_epoch
         self.accumulate_grad_batches = accumulate_grad_batches
         self.gradient_clip_val = gradient_clip_val
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(
+                "gradient_clip_algorithm must be 'norm' or 'value', got "
+                f"{gradient_clip_algorithm!r}")
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        # global grad norm of the last clip; a tensor the trainer never
+        # synchronises (None until the first clipped step)
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.log_every_n_steps = log_every_n_steps
         self.enable_checkpointing = enable_checkpointing
         self.enable_progress_bar = enable_progress_bar
@@ -645,8 +654,46 @@ class Trainer:
             self.should_stop = bool(flag.item() > 0)
 
     def _clip_gradients(self, optimizer) -> None:
+        """Clip by the global L2 norm (or by value). The norm of the last
+        clip is kept in ``last_grad_norm`` as a tensor the trainer never
+        synchronises.
+
+        - an optimizer with ``clip_grad_norm`` (the sharded one) clips
+          by the whole model's norm itself;
+        - GPU grads go through the HIP sum-of-squares kernel; a fused
+          optimizer then takes the coefficient as a multiplier inside
+          its next step, any other optimizer gets an in-place scale;
+        - CPU grads use ``torch.nn.utils.clip_grad_norm_``.
+        Under a GradScaler the scale is always in place: the scaler
+        inspects the grads, and may skip the step a deferred
+        coefficient would be waiting for.
+        """
         params = [p for g in optimizer.param_groups for p in g["params"]]
-        torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val)
+        if self.gradient_clip_algorithm == "value":
+            torch.nn.utils.clip_grad_value_(params, self.gradient_clip_val)
+            return
+        defer = self._grad_scaler is None
+        if hasattr(optimizer, "clip_grad_norm"):
+            self.last_grad_norm = optimizer.clip_grad_norm(
+                self.gradient_clip_val, defer=defer)
+            return
+        from .. import ops
+        grads = [p.grad for p in params if p.grad is not None]
+        # the kernels cover the dtypes this project trains in; anything
+        # else (fp16/fp64 grads) keeps torch's own clipping
+        if grads and ops.hip_ext_available() and all(
+                g.is_cuda and g.dtype in (torch.float32, torch.bfloat16)
+                for g in grads):
+            norm, coef = ops.clip_coef(ops.grad_sumsq(grads),
+                                       self.gradient_clip_val)
+            if defer and hasattr(optimizer, "set_grad_scale"):
+                optimizer.set_grad_scale(coef)
+            else:
+                ops.scale_grads_(grads, coef)
+            self.last_grad_norm = norm.reshape(())
+            return
+        self.last_grad_norm = torch.nn.utils.clip_grad_norm_(
+            params, self.gradient_clip_val)
 
     def _step_schedulers(self, interval: str) -> None:
         for sched, cfg in zip(self.lr_schedulers, self._lr_scheduler_cfgs):
@@ -764,4 +811,5 @@ class Trainer:
         # the launcher itself holds live process handles.
         state["_grad_scaler"] = None
         state["_wrapped_model"] = None
+        state["last_grad_norm"] = None  # a device tensor of a past fit
         return state
