@@ -111,7 +111,8 @@ class GPT2LM(LightningModule):
     def __init__(self, model_size: str = "gpt2", lr: float = 6e-4,
                  weight_decay: float = 0.1, batch_size: int = 8,
                  seq_len: int = 1024, dataset_length: int = 4096,
-                 bf16_weights: bool = True):
+                 bf16_weights: bool = True, embd_pdrop: float = 0.0,
+                 resid_pdrop: float = 0.0, attn_pdrop: float = 0.0):
         super().__init__()
         self.save_hyperparameters()
         cfg = {
@@ -121,6 +122,9 @@ class GPT2LM(LightningModule):
             "gpt2-xl": GPT2Config.gpt2_xl,
         }[model_size]()
         cfg.n_positions = max(seq_len, 1024)
+        cfg.embd_pdrop = embd_pdrop
+        cfg.resid_pdrop = resid_pdrop
+        cfg.attn_pdrop = attn_pdrop
         self.model = GPT2(cfg)
         if bf16_weights:
             from .gpt2 import to_bf16_training

@@ -26,6 +26,12 @@ class GPT2Config:
     n_embd: int = 768
     n_layer: int = 12
     n_head: int = 12
+    # dropout (published GPT-2: 0.1 on all three). embd/resid run inside
+    # the fused add+LayerNorm kernels; attn_pdrop > 0 takes attention
+    # off the hand-written flash kernels (ops/flash_attn.py).
+    embd_pdrop: float = 0.0
+    resid_pdrop: float = 0.0
+    attn_pdrop: float = 0.0
 
     @classmethod
     def gpt2(cls):
@@ -49,6 +55,7 @@ class CausalSelfAttention(nn.Module):
         super().__init__()
         assert cfg.n_embd % cfg.n_head == 0
         self.n_head = cfg.n_head
+        self.attn_pdrop = cfg.attn_pdrop
         self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
 
@@ -61,9 +68,11 @@ class CausalSelfAttention(nn.Module):
         k = k.view(B, T, self.n_head, hs).transpose(1, 2)
         v = v.view(B, T, self.n_head, hs).transpose(1, 2)
         # hand-written MFMA flash kernels when the shape qualifies
-        # (causal bf16 hs=64); SDPA (AOTriton) otherwise
+        # (causal bf16 hs=64); SDPA (AOTriton) otherwise, and always
+        # when attention dropout is on
         from ..ops.flash_attn import flash_attention
-        y = flash_attention(q, k, v)
+        y = flash_attention(
+            q, k, v, dropout_p=self.attn_pdrop if self.training else 0.0)
         y = y.transpose(1, 2).contiguous().view(B, T, C)
         return self.c_proj(y)
 
@@ -95,12 +104,14 @@ class Block(nn.Module):
         self.attn = CausalSelfAttention(cfg)
         self.ln_2 = FusedLayerNorm(cfg.n_embd)
         self.mlp = MLP(cfg)
+        self.resid_pdrop = cfg.resid_pdrop
 
     def forward(self, x):
         # standalone (unfused) path; GPT2.forward drives the fused
         # residual+LN chain across block boundaries instead
-        x = x + self.attn(self.ln_1(x))
-        x = x + self.mlp(self.ln_2(x))
+        p, tr = self.resid_pdrop, self.training
+        x = x + F.dropout(self.attn(self.ln_1(x)), p, tr)
+        x = x + F.dropout(self.mlp(self.ln_2(x)), p, tr)
         return x
 
 
@@ -137,14 +148,21 @@ class GPT2(nn.Module):
         # fused pre-norm chain: each residual add is folded into the
         # NEXT LayerNorm's forward (ops/fused_ln.py), crossing block
         # boundaries; h is always ln(x) of the current position.
-        h = self.h[0].ln_1(x)
+        # Dropout rides in the same kernels: embedding dropout in the
+        # first LayerNorm (its x_new becomes the residual stream),
+        # residual dropout on each sublayer output as it is added.
+        pe, pr = self.cfg.embd_pdrop, self.cfg.resid_pdrop
+        if pe > 0.0:
+            x, h = self.h[0].ln_1(x, dropout_p=pe)
+        else:
+            h = self.h[0].ln_1(x)
         for i, block in enumerate(self.h):
             attn_out = block.attn(h)
-            x, h = block.ln_2(attn_out, residual=x)
+            x, h = block.ln_2(attn_out, residual=x, dropout_p=pr)
             mlp_out = block.mlp(h)
             next_ln = (self.h[i + 1].ln_1 if i + 1 < len(self.h)
                        else self.ln_f)
-            x, h = next_ln(mlp_out, residual=x)
+            x, h = next_ln(mlp_out, residual=x, dropout_p=pr)
         x = h  # = ln_f(x)
         if targets is not None:
             # chunked LM-head + CE: never materializes the [B*T, V]

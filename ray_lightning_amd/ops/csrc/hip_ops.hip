@@ -1011,6 +1011,17 @@ std::vector<torch::Tensor> fused_ln_bwd(
     torch::Tensor dy, torch::Tensor x,
     c10::optional<torch::Tensor> dext, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor invstd);
+// dropout fused into the same pair, mask regenerated in backward
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           uint64_t, uint64_t>
+fused_dropout_ln_fwd(torch::Tensor sub, c10::optional<torch::Tensor> res,
+                     torch::Tensor gamma, torch::Tensor beta, double eps,
+                     double p);
+std::vector<c10::optional<torch::Tensor>> fused_dropout_ln_bwd(
+    torch::Tensor dy, torch::Tensor x,
+    c10::optional<torch::Tensor> dext, torch::Tensor gamma,
+    torch::Tensor mean, torch::Tensor invstd, double p, uint64_t seed,
+    uint64_t offset, bool has_res);
 
 
 // ===================================================================
@@ -1120,6 +1131,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused residual-add + LayerNorm forward");
   m.def("fused_ln_bwd", &fused_ln_bwd,
         "fused residual-add + LayerNorm backward");
+  m.def("fused_dropout_ln_fwd", &fused_dropout_ln_fwd,
+        "fused dropout + residual-add + LayerNorm forward");
+  m.def("fused_dropout_ln_bwd", &fused_dropout_ln_bwd,
+        "fused dropout + residual-add + LayerNorm backward");
   m.def("flash_attn_fwd", &flash_attn_fwd,
         "causal flash attention forward (hs=64, bf16, MFMA)");
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3,

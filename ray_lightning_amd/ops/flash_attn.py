@@ -7,7 +7,8 @@ flash_attn.hip) engage for causal bf16 hs=64 T%64==0 on GPU and are
 the DEFAULT: measured 0.421 ms fwd+bwd vs AOTriton SDPA's 0.710 ms on
 the GPT-2-XL shape (B=8, H=25, T=1024) — 41% faster, winning both
 directions (fwd -12%, bwd -47%); profiles/r02_flash_v3.md.
-Anything else falls back to ``F.scaled_dot_product_attention``.
+Anything else, attention dropout included, falls back to
+``F.scaled_dot_product_attention``.
 ``RLA_FLASH=0`` disables the custom path; ``RLA_FLASH_SHFL=1`` selects
 the ds_bpermute redistribution variant (debug).
 """
@@ -53,10 +54,17 @@ class _FlashAttn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
-def flash_attention(q: torch.Tensor, k: torch.Tensor,
-                    v: torch.Tensor) -> torch.Tensor:
+def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                    dropout_p: float = 0.0) -> torch.Tensor:
     """Causal attention; custom MFMA kernels when usable, SDPA
-    otherwise."""
+    otherwise.
+
+    ``dropout_p > 0`` (dropout on the attention probabilities) always
+    takes ``F.scaled_dot_product_attention``: the hand-written kernels
+    have no dropout, so attention dropout costs their speed-up."""
+    if dropout_p > 0.0:
+        return F.scaled_dot_product_attention(
+            q, k, v, dropout_p=dropout_p, is_causal=True)
     if _usable(q):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         scale = 1.0 / math.sqrt(q.shape[-1])
