@@ -27,8 +27,8 @@ class GPT2Config:
     n_layer: int = 12
     n_head: int = 12
     # dropout (published GPT-2: 0.1 on all three). embd/resid run inside
-    # the fused add+LayerNorm kernels; attn_pdrop > 0 takes attention
-    # off the hand-written flash kernels (ops/flash_attn.py).
+    # the fused add+LayerNorm kernels, attn_pdrop inside the flash
+    # attention kernels (ops/flash_attn.py); no mask is stored.
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     attn_pdrop: float = 0.0
@@ -68,8 +68,8 @@ class CausalSelfAttention(nn.Module):
         k = k.view(B, T, self.n_head, hs).transpose(1, 2)
         v = v.view(B, T, self.n_head, hs).transpose(1, 2)
         # hand-written MFMA flash kernels when the shape qualifies
-        # (causal bf16 hs=64); SDPA (AOTriton) otherwise, and always
-        # when attention dropout is on
+        # (causal bf16 hs=64), attention dropout included; SDPA
+        # (AOTriton) otherwise
         from ..ops.flash_attn import flash_attention
         y = flash_attention(
             q, k, v, dropout_p=self.attn_pdrop if self.training else 0.0)

@@ -15,6 +15,10 @@
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <ATen/hip/HIPGeneratorImpl.h>
+#include <ATen/hip/HIPGraphsUtils.cuh>
+
+#include "philox_dropout.h"
 
 namespace {
 
@@ -850,7 +854,36 @@ __device__ __forceinline__ void redist_pair(unsigned xj, unsigned yj,
   }
 }
 
-template <bool USE_PERMLANE>
+// --- attention dropout (DROPOUT instantiations of the v3 kernels) -----
+// The mask is the fused-LN convention (philox_dropout.h) applied to the
+// [B, H, T, T] probability matrix: flat i = ((bh*T + q)*T + kv), one
+// Philox call per aligned group of four kv of one q row (T % 64 == 0,
+// so a group never straddles rows). Group index of (row q, kv group
+// kv4 = kv >> 2) is (bh*T + q) * (T/4) + kv4, in 64 bits: B*H*T*T
+// passes 2^32 at shapes in use. The kernels only differ in which lane
+// makes which call; the mask is a function of (seed, offset, i) alone.
+__device__ __forceinline__ uint64_t drop_row_group(int bh, int T,
+                                                   int row) {
+  return ((uint64_t)bh * (uint64_t)T + (uint64_t)row) *
+         (uint64_t)(T >> 2);
+}
+
+__device__ __forceinline__ uint4 drop_words(const DropArgs& d,
+                                            uint64_t grp) {
+  return philox4x32_10(
+      d.k0, d.k1,
+      make_uint4(d.o0, d.o1, (uint32_t)grp, (uint32_t)(grp >> 32)));
+}
+
+// keep nibble of one call: bit w = word w kept
+__device__ __forceinline__ unsigned drop_nibble(const DropArgs& d,
+                                                uint64_t grp) {
+  const uint4 w = drop_words(d, grp);
+  return (unsigned)(w.x >= d.thr) | ((unsigned)(w.y >= d.thr) << 1) |
+         ((unsigned)(w.z >= d.thr) << 2) | ((unsigned)(w.w >= d.thr) << 3);
+}
+
+template <bool USE_PERMLANE, bool DROPOUT = false>
 // min 4 waves/EU: keeps the allocator at <=128 regs so occupancy stays
 // at the LDS-allowed 4 waves/SIMD (131 regs would drop it to 3)
 __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
@@ -858,7 +891,7 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
     const __hip_bfloat16* __restrict__ K,
     const __hip_bfloat16* __restrict__ V,
     __hip_bfloat16* __restrict__ O, float* __restrict__ LSE,
-    int T, float scale) {
+    int T, float scale, DropArgs drop) {
   const int bh = blockIdx.y;
   const int qm0 = blockIdx.x * BM3;
   if (qm0 >= T) return;
@@ -911,6 +944,25 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
       // --- S^T = K Q^T: lane gets kv = kn0+16*sub+4*g+r of column myq
       // (T5: favor the MFMA-entering wave over waves in their
       // memory/softmax phases)
+      // dropout: the tile's 16 keep bits (bit 4*sub + r) first, while
+      // only the loop-carried state is live: the generator's registers
+      // are dead again before S^T and the softmax need theirs, which
+      // keeps these instantiations at 4 waves without scratch (drawn
+      // next to the softmax they need 135 VGPRs). This lane's four r
+      // of one sub are one aligned kv group of row myq: one lane-local
+      // call per sub. Group index = wave-uniform 64-bit part + 32-bit
+      // lane part.
+      unsigned keep = 0;
+      if constexpr (DROPOUT) {
+        const uint64_t grp0 =
+            drop_row_group(bh, T, q0) + (uint64_t)(kn0 >> 2) +
+            (uint64_t)((unsigned)(lane & 15) * (unsigned)(T >> 2) +
+                       (unsigned)g);
+        #pragma unroll
+        for (int sub = 0; sub < 4; ++sub)
+          keep |= drop_nibble(drop, grp0 + 4 * sub) << (4 * sub);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       f32x4 st[4];
       __builtin_amdgcn_s_setprio(1);
       #pragma unroll
@@ -976,6 +1028,16 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
       rowsum += __shfl_xor(rowsum, 32, 64);
       l_i = l_i * corr + rowsum;
       m_i = m_new;
+      if constexpr (DROPOUT) {
+        // m, l (and LSE) are those of the undropped P; the mask goes
+        // on P alone
+        #pragma unroll
+        for (int sub = 0; sub < 4; ++sub)
+          #pragma unroll
+          for (int r = 0; r < 4; ++r)
+            st[sub][r] =
+                ((keep >> (4 * sub + r)) & 1u) ? st[sub][r] : 0.f;
+      }
       // --- P^T -> PV B-fragments, in registers -----------------------
       bf16x8 pb[2];
       #pragma unroll
@@ -1013,7 +1075,8 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
   }
 
   // --- epilogue: transpose O^T -> O rows through LDS ------------------
-  const float inv_l = (l_i > 0.f) ? 1.f / l_i : 0.f;
+  float inv_l = (l_i > 0.f) ? 1.f / l_i : 0.f;
+  if constexpr (DROPOUT) inv_l *= drop.scale;   // 1/(1-p) on kept P
   __bf16* ow = lds_o[wave];
   #pragma unroll
   for (int n = 0; n < 4; ++n)
@@ -1062,10 +1125,82 @@ std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
                      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
                      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
                      reinterpret_cast<__hip_bfloat16*>(o.data_ptr()),
-                     lse.data_ptr<float>(), T, (float)scale);
+                     lse.data_ptr<float>(), T, (float)scale, DropArgs{});
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "flash_fwd_v3: ", hipGetErrorString(e));
   return {o, lse};
+}
+
+namespace {
+
+// Shape/dtype/device rules of the dropout entry points: the v3 kernels
+// index every operand with q's extents, so every operand must have them.
+void check_flash_dropout_operand(const torch::Tensor& t,
+                                 const torch::Tensor& q,
+                                 const char* what) {
+  TORCH_CHECK(t.sizes() == q.sizes() &&
+                  t.scalar_type() == q.scalar_type() &&
+                  t.device() == q.device() && t.is_contiguous(),
+              "flash_attn_v3_dropout: ", what,
+              " must be contiguous with q's sizes, dtype and device");
+}
+
+void check_flash_dropout_q(const torch::Tensor& q, double p) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
+                  q.is_contiguous(),
+              "flash_attn_v3_dropout: bf16 contiguous GPU tensors");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == HS,
+              "flash_attn_v3_dropout: [B,H,T,64] expected");
+  TORCH_CHECK(q.size(2) % BM3 == 0 && q.size(2) > 0,
+              "flash_attn_v3_dropout: T % 64 == 0");
+  TORCH_CHECK(q.size(0) * q.size(1) <= 65535,
+              "flash_attn_v3_dropout: B*H > 65535");
+  TORCH_CHECK(p >= 0.0 && p < 1.0,
+              "flash_attn_v3_dropout: p must be in [0, 1)");
+}
+
+}  // namespace
+
+// Forward with dropout on the attention probabilities. Draws (seed,
+// offset) from the default generator of q's device, exactly as
+// fused_dropout_ln_fwd does, and returns (o, lse, seed, offset); lse is
+// that of the undropped softmax.
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
+                          torch::Tensor v, double scale, double p,
+                          bool use_permlane) {
+  check_flash_dropout_q(q, p);
+  check_flash_dropout_operand(k, q, "k");
+  check_flash_dropout_operand(v, q, "v");
+  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
+  // graph-capture-safe RNG (device-side offset) is not implemented
+  at::cuda::assertNotCapturing(
+      "flash_attn_v3_dropout: drawing the dropout seed");
+  std::pair<uint64_t, uint64_t> rng;
+  {
+    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
+        c10::nullopt,
+        at::cuda::detail::getDefaultCUDAGenerator(q.get_device()));
+    std::lock_guard<std::mutex> lock(gen->mutex_);
+    rng = gen->philox_engine_inputs(4);
+  }
+  const DropArgs drop = make_drop_args(p, rng.first, rng.second);
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  dim3 grid(T / BM3, B * H);
+  auto* kern = use_permlane ? flash_fwd_v3_kernel<true, true>
+                            : flash_fwd_v3_kernel<false, true>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
+                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
+                     reinterpret_cast<__hip_bfloat16*>(o.data_ptr()),
+                     lse.data_ptr<float>(), T, (float)scale, drop);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "flash_fwd_v3_dropout: ",
+              hipGetErrorString(e));
+  return {o, lse, rng.first, rng.second};
 }
 
 // =====================================================================
@@ -1129,25 +1264,38 @@ __device__ __forceinline__ void read_frag_tr2x2(
   }
 }
 
+// Value of lane (lane ^ X) of the same quad, X = 1 or 2. DPP quad_perm
+// ([1,0,3,2] = 0xB1, [2,3,0,1] = 0x4E) in the permlane build,
+// ds_bpermute (__shfl_xor) in the bpermute build; same result.
+template <bool USE_PERMLANE, int X>
+__device__ __forceinline__ unsigned quad_xchg(unsigned v) {
+  static_assert(X == 1 || X == 2, "quad_xchg: X is 1 or 2");
+  if (USE_PERMLANE)
+    return (unsigned)__builtin_amdgcn_update_dpp(
+        0, (int)v, X == 1 ? 0xB1 : 0x4E, 0xF, 0xF, true);
+  return (unsigned)__shfl_xor((int)v, X, 64);
+}
+
 // dK/dV v3: workgroup = 64 KV rows, 4 waves x 16 kv columns; iterate
 // q tiles of 64. C layouts put kv in lane&15 throughout:
 //   S[q][kv]   = mfma(Q_frag,  K^T B-frag)   (both direct row-major)
 //   dP[q][kv]  = mfma(dO_frag, V^T B-frag)
 //   dV^T[d][kv]= mfma(dO^T A-frag(lds), redist(P) B-frag)
 //   dK^T[d][kv]= mfma(Q^T  A-frag(lds), redist(dS) B-frag)
-template <bool USE_PERMLANE>
+template <bool USE_PERMLANE, bool DROPOUT = false>
 // min 3 waves/EU (the LDS cap): the pair-batched tr reads push regs to
 // ~172 which rounds to 2 waves without the bound. Postmortem rule:
 // verified ScratchSize stays 0 under this bound (spills + hand asm
-// were the r02 nondeterminism bug).
-__global__ __launch_bounds__(256, 3) void flash_bwd_dkv_v3_kernel(
+// were the r02 nondeterminism bug). DROPOUT spills at 170 (44-68
+// bytes), so those instantiations take 2 waves.
+__global__ __launch_bounds__(256, DROPOUT ? 2 : 3) void flash_bwd_dkv_v3_kernel(
     const __hip_bfloat16* __restrict__ Qg,
     const __hip_bfloat16* __restrict__ Kg,
     const __hip_bfloat16* __restrict__ Vg,
     const __hip_bfloat16* __restrict__ dOg,
     const float* __restrict__ LSE, const float* __restrict__ Dg,
     __hip_bfloat16* __restrict__ dK, __hip_bfloat16* __restrict__ dV,
-    int T, float scale) {
+    int T, float scale, DropArgs drop) {
   const int bh = blockIdx.y;
   const int kb0 = blockIdx.x * BM3;      // 64 KV rows per workgroup
   if (kb0 >= T) return;
@@ -1237,6 +1385,27 @@ __global__ __launch_bounds__(256, 3) void flash_bwd_dkv_v3_kernel(
             &lds_d[buf][16 * sub + 4 * g]);
         const float lse_a[4] = {lse4.x, lse4.y, lse4.z, lse4.w};
         const float d_a[4] = {d4.x, d4.y, d4.z, d4.w};
+        // dropout: bit 4r of keep16 = keep(q row r of this sub, mykv).
+        // The layout is the forward's transposed: a lane holds ONE kv
+        // and four consecutive q rows, and the four lanes of a quad
+        // hold the four kv of one aligned group. Lane j = lane&3 makes
+        // the call for row r = j (all four words are used: they are
+        // the quad's four kv), reduces it to a keep nibble at bits
+        // 4j..4j+3, and two quad exchanges OR the four nibbles
+        // together: one call per lane per sub, as in the forward.
+        unsigned keep16 = 0;
+        if constexpr (DROPOUT) {
+          const int j = lane & 3;
+          // wave-uniform 64-bit part + 32-bit lane part
+          const uint64_t grp =
+              drop_row_group(bh, T, qm0 + 16 * sub) +
+              (uint64_t)((unsigned)(4 * g + j) * (unsigned)(T >> 2) +
+                         (unsigned)(mykv >> 2));
+          unsigned nib = drop_nibble(drop, grp) << (4 * j);
+          nib |= quad_xchg<USE_PERMLANE, 1>(nib);
+          nib |= quad_xchg<USE_PERMLANE, 2>(nib);
+          keep16 = nib >> j;    // word (kv & 3) = j of every row
+        }
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qi = 16 * sub + 4 * g + r;     // tile-local q
@@ -1247,8 +1416,17 @@ __global__ __launch_bounds__(256, 3) void flash_bwd_dkv_v3_kernel(
           const float e = valid
               ? (scale * sacc[r] - lse_a[r]) * l2e : -1e30f;
           const float p = fast_exp2(e);
-          pv[sub][r] = p;
-          dsv[sub][r] = scale * p * (dpacc[r] - d_a[r]);
+          if constexpr (DROPOUT) {
+            // dV += (P o M/(1-p))^T dO: the 1/(1-p) waits for the
+            // epilogue; dS = scale * P o (M/(1-p) o dP - D)
+            const bool keep = (keep16 >> (4 * r)) & 1u;
+            pv[sub][r] = keep ? p : 0.f;
+            dsv[sub][r] = scale * p *
+                ((keep ? dpacc[r] * drop.scale : 0.f) - d_a[r]);
+          } else {
+            pv[sub][r] = p;
+            dsv[sub][r] = scale * p * (dpacc[r] - d_a[r]);
+          }
         }
       }
       // redistribute over the q axis -> B-fragments (k = q)
@@ -1322,9 +1500,14 @@ __global__ __launch_bounds__(256, 3) void flash_bwd_dkv_v3_kernel(
     #pragma unroll
     for (int n = 0; n < 4; ++n)
       #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        ew[(lane & 15) * HS + 16 * n + 4 * g + r] =
-            (__bf16)acc[n][r];
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (DROPOUT)   // dV carries the deferred 1/(1-p)
+          ew[(lane & 15) * HS + 16 * n + 4 * g + r] =
+              (__bf16)(which ? acc[n][r] : acc[n][r] * drop.scale);
+        else
+          ew[(lane & 15) * HS + 16 * n + 4 * g + r] =
+              (__bf16)acc[n][r];
+      }
     wait_lds();
     int4 t0 = *reinterpret_cast<const int4*>(ew + erow * HS + ec0);
     int4 t1 = *reinterpret_cast<const int4*>(ew + erow * HS + ec0 + 8);
@@ -1377,7 +1560,7 @@ __device__ __forceinline__ void read_frag_tr_2col(const __bf16* img,
 //   S^T[kv][q]  = mfma(K_frag,  Q^T B-frag)
 //   dP^T[kv][q] = mfma(V_frag,  dO^T B-frag)
 //   dQ^T[d][q]  = mfma(K^T A-frag(lds), redist(dS^T) B-frag)
-template <bool USE_PERMLANE>
+template <bool USE_PERMLANE, bool DROPOUT = false>
 // min 4 waves/EU: LDS allows 6, keep the allocator under 128 regs
 __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ Qg,
@@ -1385,7 +1568,8 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ Vg,
     const __hip_bfloat16* __restrict__ dOg,
     const float* __restrict__ LSE, const float* __restrict__ Dg,
-    __hip_bfloat16* __restrict__ dQ, int T, float scale) {
+    __hip_bfloat16* __restrict__ dQ, int T, float scale,
+    DropArgs drop) {
   const int bh = blockIdx.y;
   const int qm0 = blockIdx.x * BM3;
   if (qm0 >= T) return;
@@ -1450,6 +1634,22 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
             av0, dof[0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             av1, dof[1], dpt, 0, 0, 0);
+        if constexpr (DROPOUT) {
+          // the forward's layout: this lane's four r are one aligned
+          // kv group of row myq -> one lane-local call per sub;
+          // dS = scale * P o (M/(1-p) o dP - D)
+          // (group index = wave-uniform 64-bit + 32-bit lane part)
+          const uint4 w = drop_words(
+              drop, drop_row_group(bh, T, q0) +
+                        (uint64_t)((kn0 >> 2) + 4 * sub) +
+                        (uint64_t)((unsigned)(lane & 15) *
+                                       (unsigned)(T >> 2) +
+                                   (unsigned)g));
+          dpt[0] = w.x >= drop.thr ? dpt[0] * drop.scale : 0.f;
+          dpt[1] = w.y >= drop.thr ? dpt[1] * drop.scale : 0.f;
+          dpt[2] = w.z >= drop.thr ? dpt[2] * drop.scale : 0.f;
+          dpt[3] = w.w >= drop.thr ? dpt[3] * drop.scale : 0.f;
+        }
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kvr = kn0 + 16 * sub + 4 * g + r;
@@ -1543,7 +1743,7 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
                      lse.data_ptr<float>(), D.data_ptr<float>(),
                      reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
                      reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
-                     T, (float)scale);
+                     T, (float)scale, DropArgs{});
   hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream,
                      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
                      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
@@ -1551,9 +1751,68 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
                      reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
                      lse.data_ptr<float>(), D.data_ptr<float>(),
                      reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
-                     T, (float)scale);
+                     T, (float)scale, DropArgs{});
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "flash_bwd_v3: ", hipGetErrorString(e));
+  return {dq, dk, dv};
+}
+
+// Backward of flash_attn_fwd_v3_dropout: the mask is drawn again from
+// the (seed, offset) the forward returned. D = rowsum(dO o O) is the
+// dropout-free expression (O already carries the mask), so the pre
+// kernel is shared.
+std::vector<torch::Tensor> flash_attn_bwd_v3_dropout(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
+    double p, uint64_t seed, uint64_t offset, bool use_permlane) {
+  check_flash_dropout_q(q, p);
+  dout = dout.contiguous();
+  check_flash_dropout_operand(k, q, "k");
+  check_flash_dropout_operand(v, q, "v");
+  check_flash_dropout_operand(o, q, "o");
+  check_flash_dropout_operand(dout, q, "dout");
+  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.device() == q.device() &&
+                  lse.numel() == (int64_t)B * H * T,
+              "flash_attn_v3_dropout: lse must be fp32 [B,H,T] on q's "
+              "device");
+  const DropArgs drop = make_drop_args(p, seed, offset);
+  auto dq = torch::empty_like(q);
+  auto dk = torch::empty_like(k);
+  auto dv = torch::empty_like(v);
+  auto D = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  const long total_rows = (long)B * H * T;
+  hipLaunchKernelGGL(flash_bwd_pre_kernel,
+                     dim3((total_rows + 63) / 64), dim3(256), 0, stream,
+                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
+                     D.data_ptr<float>(), total_rows);
+  dim3 grid(T / BM3, B * H);
+  auto* kdkv = use_permlane ? flash_bwd_dkv_v3_kernel<true, true>
+                            : flash_bwd_dkv_v3_kernel<false, true>;
+  auto* kdq = use_permlane ? flash_bwd_dq_v3_kernel<true, true>
+                           : flash_bwd_dq_v3_kernel<false, true>;
+  hipLaunchKernelGGL(kdkv, grid, dim3(256), 0, stream,
+                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+                     lse.data_ptr<float>(), D.data_ptr<float>(),
+                     reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
+                     reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
+                     T, (float)scale, drop);
+  hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream,
+                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+                     lse.data_ptr<float>(), D.data_ptr<float>(),
+                     reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
+                     T, (float)scale, drop);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "flash_bwd_v3_dropout: ", hipGetErrorString(e));
   return {dq, dk, dv};
 }
 

@@ -27,6 +27,8 @@
 #include <ATen/hip/HIPGeneratorImpl.h>
 #include <ATen/hip/HIPGraphsUtils.cuh>
 
+#include "philox_dropout.h"
+
 #define CHECK_HIP_LN(cmd)                                                  \
   do {                                                                     \
     hipError_t e = (cmd);                                                  \
@@ -495,29 +497,8 @@ std::vector<torch::Tensor> fused_ln_bwd(
 // ====================================================================
 namespace {
 
-struct DropArgs {
-  uint32_t k0, k1;   // Philox key = seed
-  uint32_t o0, o1;   // counter low half = offset / 4
-  uint32_t thr;      // drop iff word < thr
-  float scale;       // 1 / (1-p)
-};
-
-__device__ __forceinline__ uint4 philox4x32_10(uint32_t k0, uint32_t k1,
-                                               uint4 c) {
-  constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u;
-  constexpr uint32_t kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-  #pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    // one 32x32->64 multiply gives the hi and lo words together
-    const uint64_t p0 = (uint64_t)kM0 * c.x;
-    const uint64_t p1 = (uint64_t)kM1 * c.z;
-    c = make_uint4((uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1,
-                   (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0);
-    k0 += kW0;
-    k1 += kW1;
-  }
-  return c;
-}
+// DropArgs, philox4x32_10 and make_drop_args: philox_dropout.h, shared
+// with the flash attention dropout kernels.
 
 // keep bits for the V elements starting at flat element e0 (e0 % 4 == 0)
 template <int V>
@@ -704,20 +685,6 @@ __global__ __launch_bounds__(kT) void ln_drop_bwd_dx_kernel(
           *reinterpret_cast<const int4*>(sv);
     }
   }
-}
-
-DropArgs make_drop_args(double p, uint64_t seed, uint64_t offset) {
-  TORCH_CHECK(p >= 0.0 && p < 1.0, "fused_dropout_ln: p must be in [0, 1)");
-  DropArgs d;
-  d.k0 = (uint32_t)seed;
-  d.k1 = (uint32_t)(seed >> 32);
-  const uint64_t ctr = offset >> 2;
-  d.o0 = (uint32_t)ctr;
-  d.o1 = (uint32_t)(ctr >> 32);
-  d.thr = (uint32_t)std::min<uint64_t>((uint64_t)(p * 4294967296.0),
-                                       0xFFFFFFFFull);
-  d.scale = (float)(1.0 / (1.0 - p));
-  return d;
 }
 
 // dgamma/dbeta do not depend on the mask: the same three launches as

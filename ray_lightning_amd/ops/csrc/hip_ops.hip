@@ -991,6 +991,16 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
     bool use_permlane);
+// v3 with dropout on the attention probabilities (mask regenerated in
+// backward from the (seed, offset) the forward returns)
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
+                          torch::Tensor v, double scale, double p,
+                          bool use_permlane);
+std::vector<torch::Tensor> flash_attn_bwd_v3_dropout(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
+    double p, uint64_t seed, uint64_t offset, bool use_permlane);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor perm_probe(torch::Tensor M, torch::Tensor B,
                          long variant);
@@ -1143,6 +1153,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "causal flash attention backward");
   m.def("flash_attn_bwd_v3", &flash_attn_bwd_v3,
         "swapped-operand MFMA flash attention bwd (v3)");
+  m.def("flash_attn_fwd_v3_dropout", &flash_attn_fwd_v3_dropout,
+        "v3 flash attention fwd with attention dropout");
+  m.def("flash_attn_bwd_v3_dropout", &flash_attn_bwd_v3_dropout,
+        "v3 flash attention bwd with attention dropout");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("perm_probe", &perm_probe,
         "C-layout -> A-fragment bpermute redistribution probe");
