@@ -15,7 +15,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from ..ops.fused_bn import FusedBatchNorm2d
+from ..ops.fused_bn import FusedBatchNorm2d, bn_fusions_enabled
 
 
 class Bottleneck(nn.Module):
@@ -34,11 +34,22 @@ class Bottleneck(nn.Module):
         self.bn3 = FusedBatchNorm2d(out_ch, relu=True)  # fused add+relu
         self.downsample = downsample
         self.stride = stride
+        # conv + BN downsample: both BNs of the junction run as one
+        # dual-BN kernel set (RLA_BN_FUSIONS, read once here)
+        self._dual_bn = bn_fusions_enabled() and \
+            isinstance(downsample, nn.Sequential) and \
+            len(downsample) == 2 and \
+            isinstance(downsample[0], nn.Conv2d) and \
+            isinstance(downsample[1], FusedBatchNorm2d)
 
     def forward(self, x):
         identity = x
         out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
+        if self._dual_bn:
+            return self.bn3.forward_dual(self.conv3(out),
+                                         self.downsample[0](x),
+                                         self.downsample[1])
         if self.downsample is not None:
             identity = self.downsample(x)
         return self.bn3(self.conv3(out), identity)
@@ -58,6 +69,8 @@ class ResNet(nn.Module):
         self.layer4 = self._make_layer(512, layers[3], stride=2)
         self.avgpool = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(512 * Bottleneck.expansion, num_classes)
+        # stem BN+ReLU+maxpool as one kernel set (RLA_BN_FUSIONS)
+        self._stem_pool = bn_fusions_enabled()
 
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
@@ -87,7 +100,11 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.bn1(self.conv1(x)))
+        x = self.conv1(x)
+        if self._stem_pool:
+            x = self.bn1.forward_pool(x, self.maxpool)
+        else:
+            x = self.maxpool(self.bn1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)

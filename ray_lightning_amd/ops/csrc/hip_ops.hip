@@ -974,6 +974,27 @@ std::vector<torch::Tensor> fused_bn_bwd(
     torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
     torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma,
     bool relu, bool has_res);
+// BN+ReLU+MaxPool(3,2,1) for the stem and dual BN(+ReLU) for the
+// downsample junction — defined in fused_bn.hip
+std::vector<torch::Tensor> fused_bn_relu_pool_fwd(
+    torch::Tensor x, torch::Tensor gamma, torch::Tensor beta,
+    torch::Tensor running_mean, torch::Tensor running_var,
+    double momentum, double eps);
+std::vector<torch::Tensor> fused_bn_relu_pool_bwd(
+    torch::Tensor dpool, torch::Tensor code, torch::Tensor x,
+    torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma);
+std::vector<torch::Tensor> fused_bn_dual_fwd(
+    torch::Tensor x3, torch::Tensor xd, torch::Tensor gamma3,
+    torch::Tensor beta3, torch::Tensor running_mean3,
+    torch::Tensor running_var3, torch::Tensor gammad,
+    torch::Tensor betad, torch::Tensor running_meand,
+    torch::Tensor running_vard, double momentum3, double momentumd,
+    double eps3, double epsd);
+std::vector<torch::Tensor> fused_bn_dual_bwd(
+    torch::Tensor dy, torch::Tensor mask, torch::Tensor x3,
+    torch::Tensor xd, torch::Tensor mean3, torch::Tensor invstd3,
+    torch::Tensor gamma3, torch::Tensor meand, torch::Tensor invstdd,
+    torch::Tensor gammad);
 
 // flash attention (causal, hs=64) — defined in flash_attn.hip
 std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q,
@@ -1137,6 +1158,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused NHWC BN(+ReLU)(+residual) forward");
   m.def("fused_bn_bwd", &fused_bn_bwd,
         "fused NHWC BN(+ReLU)(+residual) backward");
+  m.def("fused_bn_relu_pool_fwd", &fused_bn_relu_pool_fwd,
+        "fused NHWC BN+ReLU+MaxPool(3,2,1) forward");
+  m.def("fused_bn_relu_pool_bwd", &fused_bn_relu_pool_bwd,
+        "fused NHWC BN+ReLU+MaxPool(3,2,1) backward");
+  m.def("fused_bn_dual_fwd", &fused_bn_dual_fwd,
+        "fused NHWC relu(BN(x3) + BN(xd)) forward");
+  m.def("fused_bn_dual_bwd", &fused_bn_dual_bwd,
+        "fused NHWC relu(BN(x3) + BN(xd)) backward");
   m.def("fused_ln_fwd", &fused_ln_fwd,
         "fused residual-add + LayerNorm forward");
   m.def("fused_ln_bwd", &fused_ln_bwd,
