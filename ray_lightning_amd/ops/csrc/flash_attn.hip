@@ -1,12 +1,32 @@
 // Flash attention (causal, hs=64, bf16) — hand-written CDNA4 MFMA
-// kernels. AOTriton's SDPA kernels on gfx950 measure ~186 TF/s
-// causal-effective forward and ~115 TF/s backward on the GPT-2 shapes
-// (profiles/r01_gpt2xl_1gpu_baseline.md); these kernels use the
-// guide's plain-HIP GEMM idioms (LDS-staged tiles, 16x16x32 MFMA,
-// flash online softmax), 32 rows per wave (2 M-halves), per-wave
-// skipping of fully-masked diagonal tiles.
+// kernels, the "v3" design (the r01 32-rows-per-wave kernels lost to it
+// 2.7x and live in git history; profiles/r02_flash_v3.md has the
+// measurements).
 //
-// Layout: q, k, v are [B, H, T, 64] bf16 contiguous. Causal only.
+// Kernels: flash_fwd_v3_kernel, flash_bwd_pre_kernel (D = rowsum(dO o
+// O)), flash_bwd_dkv_v3_kernel, flash_bwd_dq_v3_kernel. Each of the
+// three v3 kernels is instantiated for DROPOUT false (p = 0, the
+// default training path) and true (Philox mask on the probabilities),
+// and for USE_PERMLANE true (what training runs) and false (the
+// ds_bpermute redistribution, RLA_FLASH_SHFL=1, debug).
+// All three share one structure: a workgroup owns 64 rows (4 waves x
+// 16), walks the other axis in tiles of 64 staged through
+// double-buffered XOR-swizzled LDS images (issue-early / write-late),
+// computes the TRANSPOSED score tile with 16x16x32 MFMAs so that the
+// softmax axis is lane-local, and turns the C-layout result into the
+// next MFMA's B-fragment in registers (permlane32/16 swaps) instead of
+// through LDS. Tiles above the causal diagonal are skipped per wave.
+//
+// Host side (after the kernels): one set of operand checks, one forward
+// and one backward launcher, and the four exported entry points
+// flash_attn_{fwd,bwd}_v3[_dropout] that ops/flash_attn.py calls.
+//
+// Last in the file: flash_fwd_v4_kernel / flash_attn_fwd_v4, the
+// 32x32x16 forward experiment (slower than v3, forward only, not wired
+// into ops/flash_attn.py).
+//
+// Layout: q, k, v are [B, H, T, 64] bf16 contiguous, T % 64 == 0.
+// Causal only.
 // Fragment maps verified by mfma_probe (tests/test_flash_attn_gpu.py):
 //   A[16Mx32K]: lane l elem i -> row l&15,  k (l>>4)*8+i
 //   B[32Kx16N]: lane l elem i -> col l&15,  k (l>>4)*8+i
@@ -26,8 +46,6 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int HS = 64;      // head size (fixed)
-constexpr int WM = 32;      // query rows per wave (2 MFMA M-halves)
-constexpr int BM = 128;     // query rows per workgroup (4 waves)
 constexpr int BN = 64;      // key/value rows per tile
 constexpr float kNegInf = -1e30f;
 
@@ -40,18 +58,6 @@ __device__ __forceinline__ float fast_exp2(float x) {
   return __builtin_amdgcn_exp2f(x);
 }
 
-__device__ __forceinline__ float row_reduce_max(float v) {
-  #pragma unroll
-  for (int w = 8; w >= 1; w >>= 1)
-    v = fmaxf(v, __shfl_xor(v, w, 64));
-  return v;
-}
-__device__ __forceinline__ float row_reduce_sum(float v) {
-  #pragma unroll
-  for (int w = 8; w >= 1; w >>= 1)
-    v += __shfl_xor(v, w, 64);
-  return v;
-}
 __device__ __forceinline__ void wait_lds() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
@@ -68,24 +74,6 @@ __device__ __forceinline__ bf16x8 load_frag_rowmajor(
       *reinterpret_cast<const int4*>(p + off);
   return v;
 }
-
-// cooperative transpose-stage of a [BN, HS] tile into dst[HS][BN]
-__device__ __forceinline__ void stage_transposed(
-    __bf16* dst, const __hip_bfloat16* src, int row0) {
-  const int r = threadIdx.x >> 3;
-  const int c0 = (threadIdx.x & 7) * 8;
-  #pragma unroll
-  for (int rep = 0; rep < 2; ++rep) {
-    const int row = r + rep * 32;
-    bf16x8 t;
-    *reinterpret_cast<int4*>(&t) = *reinterpret_cast<const int4*>(
-        src + (long)(row0 + row) * HS + c0);
-    #pragma unroll
-    for (int i = 0; i < 8; ++i)
-      dst[(c0 + i) * BN + row] = t[i];
-  }
-}
-
 
 // --- XOR-swizzled transpose image (v3) --------------------------------
 // Image: img[d][kv] bf16, row = 128 B. Bank index depends on byte%256
@@ -158,34 +146,9 @@ __device__ __forceinline__ bf16x8 read_frag_swz(const __bf16* img,
 // block — rows = lanes 4r..4r+3 — and lane j receives column j).
 // Fragment: row = col16 + (lane&15), k elems i = source rows
 // krow0 + 8*(lane>>4) + i. Rows are swizzle-independent (each lane
-// addresses its own 8 B segment inside one granule).
-__device__ __forceinline__ bf16x8 read_frag_tr(const __bf16* img,
-                                               int krow0, int col16,
-                                               int lane) {
-  const int j = lane & 15;
-  const int g = lane >> 4;
-  const unsigned base =
-      (unsigned)(size_t)(__attribute__((address_space(3))) const char*)
-          (const void*)img;
-  const int r0 = krow0 + 8 * g + (j >> 2);
-  const int cb = (col16 + 4 * (j & 3)) * 2;
-  const unsigned a0 = base + (unsigned)swz_off(r0, cb);
-  const unsigned a1 = base + (unsigned)swz_off(r0 + 4, cb);
-  typedef __attribute__((ext_vector_type(2))) unsigned uint2v;
-  uint2v lo, hi;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n"
-      "ds_read_b64_tr_b16 %1, %3\n"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(lo), "=&v"(hi)
-      : "v"(a0), "v"(a1)
-      : "memory");
-  bf16x8 v;
-  unsigned* w = reinterpret_cast<unsigned*>(&v);
-  w[0] = lo[0]; w[1] = lo[1]; w[2] = hi[0]; w[3] = hi[1];
-  return v;
-}
-
+// addresses its own 8 B segment inside one granule). The readers below
+// batch several such fragments in front of a single lgkm drain.
+//
 // Paired variant for the fwd PV loop: BOTH kv chunks' transposed
 // fragments of one 16-col block from one image, single lgkm drain
 // (separate absolute row bases keep the swizzle sel correct).
@@ -223,591 +186,19 @@ __device__ __forceinline__ void read_frag_tr_2row(const __bf16* img,
   wb[0] = rb0[0]; wb[1] = rb0[1]; wb[2] = rb1[0]; wb[3] = rb1[1];
 }
 
-// ---------------------------------------------------------------------
-// forward
-// ---------------------------------------------------------------------
-__global__ __launch_bounds__(256) void flash_fwd_kernel(
-    const __hip_bfloat16* __restrict__ Q,
-    const __hip_bfloat16* __restrict__ K,
-    const __hip_bfloat16* __restrict__ V,
-    __hip_bfloat16* __restrict__ O, float* __restrict__ LSE,
-    int T, float scale) {
-  const int bh = blockIdx.y;
-  const int qm0 = blockIdx.x * BM;
-  if (qm0 >= T) return;
-  const long base = (long)bh * T * HS;
-  const __hip_bfloat16* q = Q + base;
-  const __hip_bfloat16* k = K + base;
-  const __hip_bfloat16* v = V + base;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wrow0 = qm0 + wave * WM;   // wave's first query row
-  const int col0 = lane & 15;
-
-  // V^T double-buffered: tile i writes buf[i&1] while others still
-  // read buf[(i-1)&1] -> ONE barrier per tile instead of two
-  __shared__ __bf16 lds_vt[2][HS * BN];       // V^T [hs][kv] 16 KB
-  __shared__ __bf16 lds_p[4][WM * BN];        // per-wave P   16 KB
-
-  bf16x8 qf[2][2];  // [m-half][k-chunk]
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-      qf[mh][kk] = load_frag_rowmajor(q, wrow0 + mh * 16, kk, lane, HS);
-
-  float m_i[2][4], l_i[2][4];
-  f32x4 o_acc[2][4];
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh) {
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      m_i[mh][r] = kNegInf;
-      l_i[mh][r] = 0.f;
-    }
-    #pragma unroll
-    for (int n = 0; n < 4; ++n)
-      o_acc[mh][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-
-  const float l2e = 1.4426950408889634f * scale;
-  const int kv_end = qm0 + BM;
-  int buf = 0;
-  for (int kn0 = 0; kn0 < kv_end && kn0 < T; kn0 += BN, buf ^= 1) {
-    stage_transposed(lds_vt[buf], v, kn0);
-    __syncthreads();
-    // waves whose every query row is below this KV tile skip compute
-    const bool active = kn0 <= wrow0 + WM - 1;
-    if (active) {
-      // --- S = Q K^T ------------------------------------------------
-      f32x4 s_acc[2][4];
-      #pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        bf16x8 bf0 = load_frag_rowmajor(k, kn0 + 16 * n, 0, lane, HS);
-        bf16x8 bf1 = load_frag_rowmajor(k, kn0 + 16 * n, 1, lane, HS);
-        #pragma unroll
-        for (int mh = 0; mh < 2; ++mh) {
-          s_acc[mh][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              qf[mh][0], bf0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          s_acc[mh][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              qf[mh][1], bf1, s_acc[mh][n], 0, 0, 0);
-        }
-      }
-      // --- causal mask (diagonal tiles only) ------------------------
-      if (kn0 + BN > wrow0) {
-        #pragma unroll
-        for (int mh = 0; mh < 2; ++mh)
-          #pragma unroll
-          for (int n = 0; n < 4; ++n)
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int qrow = wrow0 + mh * 16 + (lane >> 4) * 4 + r;
-              if (kn0 + 16 * n + col0 > qrow)
-                s_acc[mh][n][r] = kNegInf;
-            }
-      }
-      // --- online softmax -------------------------------------------
-      #pragma unroll
-      for (int mh = 0; mh < 2; ++mh) {
-        float p_scale[4];
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float mx = fmaxf(fmaxf(s_acc[mh][0][r], s_acc[mh][1][r]),
-                           fmaxf(s_acc[mh][2][r], s_acc[mh][3][r]));
-          mx = row_reduce_max(mx);
-          const float m_new = fmaxf(m_i[mh][r], mx);
-          const float corr = exp2f((m_i[mh][r] - m_new) * l2e);
-          float rowsum = 0.f;
-          #pragma unroll
-          for (int n = 0; n < 4; ++n) {
-            const float p = (s_acc[mh][n][r] <= kNegInf * 0.5f)
-                ? 0.f : exp2f((s_acc[mh][n][r] - m_new) * l2e);
-            s_acc[mh][n][r] = p;
-            rowsum += p;
-          }
-          rowsum = row_reduce_sum(rowsum);
-          l_i[mh][r] = l_i[mh][r] * corr + rowsum;
-          m_i[mh][r] = m_new;
-          p_scale[r] = corr;
-        }
-        #pragma unroll
-        for (int n = 0; n < 4; ++n)
-          #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            o_acc[mh][n][r] *= p_scale[r];
-      }
-      // --- stage P --------------------------------------------------
-      __bf16* pw = lds_p[wave];
-      #pragma unroll
-      for (int mh = 0; mh < 2; ++mh)
-        #pragma unroll
-        for (int n = 0; n < 4; ++n)
-          #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            pw[(mh * 16 + (lane >> 4) * 4 + r) * BN + 16 * n + col0] =
-                (__bf16)s_acc[mh][n][r];
-      wait_lds();
-      // --- O += P V -------------------------------------------------
-      #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 pa[2];
-        #pragma unroll
-        for (int mh = 0; mh < 2; ++mh)
-          *reinterpret_cast<int4*>(&pa[mh]) =
-              *reinterpret_cast<const int4*>(
-                  pw + (mh * 16 + (lane & 15)) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-        #pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          bf16x8 vb;
-          *reinterpret_cast<int4*>(&vb) =
-              *reinterpret_cast<const int4*>(
-                  lds_vt[buf] + (16 * n + col0) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-          #pragma unroll
-          for (int mh = 0; mh < 2; ++mh)
-            o_acc[mh][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                pa[mh], vb, o_acc[mh][n], 0, 0, 0);
-        }
-      }
-    }
-    // no trailing barrier: next tile writes the OTHER V^T buffer
-  }
-
-  // --- epilogue -----------------------------------------------------
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qrow = wrow0 + mh * 16 + (lane >> 4) * 4 + r;
-      const float inv_l = (l_i[mh][r] > 0.f) ? 1.f / l_i[mh][r] : 0.f;
-      #pragma unroll
-      for (int n = 0; n < 4; ++n)
-        O[base + (long)qrow * HS + 16 * n + col0] =
-            __float2bfloat16(o_acc[mh][n][r] * inv_l);
-      if (col0 == 0)
-        LSE[(long)bh * T + qrow] =
-            m_i[mh][r] * scale + logf(fmaxf(l_i[mh][r], 1e-30f));
-    }
-}
-
-}  // namespace
-
-std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q,
-                                          torch::Tensor k,
-                                          torch::Tensor v,
-                                          double scale) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
-              q.is_contiguous() && k.is_contiguous() &&
-              v.is_contiguous(), "flash_attn_fwd: bf16 contiguous");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == HS,
-              "flash_attn_fwd: [B,H,T,64] expected");
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
-  TORCH_CHECK(T % BM == 0, "flash_attn_fwd: T % 128 == 0");
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  dim3 grid(T / BM, B * H);
-  hipLaunchKernelGGL(flash_fwd_kernel, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<__hip_bfloat16*>(o.data_ptr()),
-                     lse.data_ptr<float>(), T, (float)scale);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "flash_fwd: ", hipGetErrorString(e));
-  return {o, lse};
-}
-
-// =====================================================================
-// backward
-// =====================================================================
-namespace {
-
-// D = rowsum(dO * O), fp32
-__global__ __launch_bounds__(256) void flash_bwd_pre_kernel(
-    const __hip_bfloat16* __restrict__ dO,
-    const __hip_bfloat16* __restrict__ O, float* __restrict__ D,
-    long total_rows) {
-  const long row = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
-  if (row >= total_rows) return;
-  const int c0 = (threadIdx.x & 3) * 16;
-  float s = 0.f;
-  #pragma unroll
-  for (int c = 0; c < 16; c += 8) {
-    bf16x8 a, b;
-    *reinterpret_cast<int4*>(&a) = *reinterpret_cast<const int4*>(
-        dO + row * HS + c0 + c);
-    *reinterpret_cast<int4*>(&b) = *reinterpret_cast<const int4*>(
-        O + row * HS + c0 + c);
-    #pragma unroll
-    for (int i = 0; i < 8; ++i)
-      s += (float)a[i] * (float)b[i];
-  }
-  #pragma unroll
-  for (int w = 1; w <= 2; w <<= 1)
-    s += __shfl_xor(s, w, 64);
-  if ((threadIdx.x & 3) == 0) D[row] = s;
-}
-
-// dK/dV: one workgroup per 128 KV rows; waves own 32 KV rows
-__global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
-    const __hip_bfloat16* __restrict__ Q,
-    const __hip_bfloat16* __restrict__ K,
-    const __hip_bfloat16* __restrict__ V,
-    const __hip_bfloat16* __restrict__ dOg,
-    const float* __restrict__ LSE, const float* __restrict__ Dg,
-    __hip_bfloat16* __restrict__ dK, __hip_bfloat16* __restrict__ dV,
-    int T, float scale) {
-  const int bh = blockIdx.y;
-  const int kb0 = blockIdx.x * BM;   // 128 KV rows per block
-  if (kb0 >= T) return;
-  const long base = (long)bh * T * HS;
-  const __hip_bfloat16* q = Q + base;
-  const __hip_bfloat16* k = K + base;
-  const __hip_bfloat16* v = V + base;
-  const __hip_bfloat16* dO = dOg + base;
-  const float* lse = LSE + (long)bh * T;
-  const float* Drow = Dg + (long)bh * T;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wkv0 = kb0 + wave * WM;   // wave's first KV row
-  const int col0 = lane & 15;
-
-  __shared__ __bf16 lds_dot[HS * BN];     // dO^T [hs][q]   8 KB
-  __shared__ __bf16 lds_qt[HS * BN];      // Q^T  [hs][q]   8 KB
-  __shared__ __bf16 lds_pt[4][WM * BN];   // P^T  per wave 16 KB
-  __shared__ __bf16 lds_dst[4][WM * BN];  // dS^T per wave 16 KB
-  __shared__ float lds_lse[BN];
-  __shared__ float lds_d[BN];
-
-  bf16x8 kf[2][2], vf[2][2];  // [kv-half][k-chunk]
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      kf[mh][kk] = load_frag_rowmajor(k, wkv0 + mh * 16, kk, lane, HS);
-      vf[mh][kk] = load_frag_rowmajor(v, wkv0 + mh * 16, kk, lane, HS);
-    }
-
-  f32x4 dv_acc[2][4], dk_acc[2][4];
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      dv_acc[mh][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dk_acc[mh][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-
-  const float l2e = 1.4426950408889634f;
-
-  for (int qm0 = kb0; qm0 < T; qm0 += BN) {  // q tiles of 64 rows
-    stage_transposed(lds_dot, dO, qm0);
-    stage_transposed(lds_qt, q, qm0);
-    if (threadIdx.x < BN) {
-      lds_lse[threadIdx.x] = lse[qm0 + threadIdx.x];
-      lds_d[threadIdx.x] = Drow[qm0 + threadIdx.x];
-    }
-    __syncthreads();
-    // skip when every q row here is below the wave's first KV row
-    const bool active = wkv0 <= qm0 + BN - 1;
-    if (active) {
-      __bf16* pt = lds_pt[wave];
-      __bf16* dst = lds_dst[wave];
-      #pragma unroll
-      for (int mh = 0; mh < 2; ++mh) {
-        #pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          // S^T = K Q^T ; dP^T = V dO^T   [16 kv, 16 q] tiles
-          bf16x8 bq0 = load_frag_rowmajor(q, qm0 + 16 * n, 0, lane, HS);
-          bf16x8 bq1 = load_frag_rowmajor(q, qm0 + 16 * n, 1, lane, HS);
-          bf16x8 bd0 = load_frag_rowmajor(dO, qm0 + 16 * n, 0, lane,
-                                          HS);
-          bf16x8 bd1 = load_frag_rowmajor(dO, qm0 + 16 * n, 1, lane,
-                                          HS);
-          f32x4 st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              kf[mh][0], bq0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              kf[mh][1], bq1, st, 0, 0, 0);
-          f32x4 dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              vf[mh][0], bd0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              vf[mh][1], bd1, dpt, 0, 0, 0);
-          const int qcol = 16 * n + col0;
-          const float lse_q = lds_lse[qcol];
-          const float d_q = lds_d[qcol];
-          #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int kvrow = wkv0 + mh * 16 + (lane >> 4) * 4 + r;
-            const bool valid = (qm0 + qcol) >= kvrow;
-            const float p = valid
-                ? fast_exp2((scale * st[r] - lse_q) * l2e) : 0.f;
-            const float ds = valid
-                ? scale * p * (dpt[r] - d_q) : 0.f;
-            pt[(mh * 16 + (lane >> 4) * 4 + r) * BN + qcol] =
-                (__bf16)p;
-            dst[(mh * 16 + (lane >> 4) * 4 + r) * BN + qcol] =
-                (__bf16)ds;
-          }
-        }
-      }
-      wait_lds();
-      // dV += P^T dO (dO^T image); dK += dS^T Q (Q^T image)
-      #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 pa[2], da[2];
-        #pragma unroll
-        for (int mh = 0; mh < 2; ++mh) {
-          *reinterpret_cast<int4*>(&pa[mh]) =
-              *reinterpret_cast<const int4*>(
-                  pt + (mh * 16 + (lane & 15)) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-          *reinterpret_cast<int4*>(&da[mh]) =
-              *reinterpret_cast<const int4*>(
-                  dst + (mh * 16 + (lane & 15)) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-        }
-        #pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          bf16x8 bdo, bq;
-          *reinterpret_cast<int4*>(&bdo) =
-              *reinterpret_cast<const int4*>(
-                  lds_dot + (16 * n + col0) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-          *reinterpret_cast<int4*>(&bq) =
-              *reinterpret_cast<const int4*>(
-                  lds_qt + (16 * n + col0) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-          #pragma unroll
-          for (int mh = 0; mh < 2; ++mh) {
-            dv_acc[mh][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                pa[mh], bdo, dv_acc[mh][n], 0, 0, 0);
-            dk_acc[mh][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                da[mh], bq, dk_acc[mh][n], 0, 0, 0);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int kvrow = wkv0 + mh * 16 + (lane >> 4) * 4 + r;
-      #pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        dK[base + (long)kvrow * HS + 16 * n + col0] =
-            __float2bfloat16(dk_acc[mh][n][r]);
-        dV[base + (long)kvrow * HS + 16 * n + col0] =
-            __float2bfloat16(dv_acc[mh][n][r]);
-      }
-    }
-}
-
-// dQ: one workgroup per 128 query rows; waves own 32 rows
-__global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
-    const __hip_bfloat16* __restrict__ Q,
-    const __hip_bfloat16* __restrict__ K,
-    const __hip_bfloat16* __restrict__ V,
-    const __hip_bfloat16* __restrict__ dOg,
-    const float* __restrict__ LSE, const float* __restrict__ Dg,
-    __hip_bfloat16* __restrict__ dQ, int T, float scale) {
-  const int bh = blockIdx.y;
-  const int qm0 = blockIdx.x * BM;
-  if (qm0 >= T) return;
-  const long base = (long)bh * T * HS;
-  const __hip_bfloat16* q = Q + base;
-  const __hip_bfloat16* k = K + base;
-  const __hip_bfloat16* v = V + base;
-  const __hip_bfloat16* dO = dOg + base;
-  const float* lse = LSE + (long)bh * T;
-  const float* Drow = Dg + (long)bh * T;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wrow0 = qm0 + wave * WM;
-  const int col0 = lane & 15;
-
-  __shared__ __bf16 lds_kt[HS * BN];      // K^T [hs][kv]
-  __shared__ __bf16 lds_ds[4][WM * BN];   // per-wave dS
-
-  bf16x8 qf[2][2], dof[2][2];
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      qf[mh][kk] = load_frag_rowmajor(q, wrow0 + mh * 16, kk, lane, HS);
-      dof[mh][kk] = load_frag_rowmajor(dO, wrow0 + mh * 16, kk, lane,
-                                       HS);
-    }
-  float lse_r[2][4], d_r[2][4];
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qrow = wrow0 + mh * 16 + (lane >> 4) * 4 + r;
-      lse_r[mh][r] = lse[qrow];
-      d_r[mh][r] = Drow[qrow];
-    }
-
-  f32x4 dq_acc[2][4];
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int n = 0; n < 4; ++n)
-      dq_acc[mh][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const float l2e = 1.4426950408889634f;
-  const int kv_end = qm0 + BM;
-  for (int kn0 = 0; kn0 < kv_end && kn0 < T; kn0 += BN) {
-    {  // stage K^T image (dQ's B operand contracts over kv)
-      const int r = threadIdx.x >> 3;
-      const int c0 = (threadIdx.x & 7) * 8;
-      #pragma unroll
-      for (int rep = 0; rep < 2; ++rep) {
-        const int row = r + rep * 32;
-        bf16x8 t;
-        *reinterpret_cast<int4*>(&t) = *reinterpret_cast<const int4*>(
-            k + (long)(kn0 + row) * HS + c0);
-        #pragma unroll
-        for (int i = 0; i < 8; ++i)
-          lds_kt[(c0 + i) * BN + row] = t[i];
-      }
-    }
-    __syncthreads();
-    const bool active = kn0 <= wrow0 + WM - 1;
-    if (active) {
-      __bf16* dsw = lds_ds[wave];
-      #pragma unroll
-      for (int mh = 0; mh < 2; ++mh) {
-        #pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          bf16x8 bk0 = load_frag_rowmajor(k, kn0 + 16 * n, 0, lane, HS);
-          bf16x8 bk1 = load_frag_rowmajor(k, kn0 + 16 * n, 1, lane, HS);
-          // dP = dO V^T contracts over hs -> row-major V fragments
-          bf16x8 bv0 = load_frag_rowmajor(v, kn0 + 16 * n, 0, lane, HS);
-          bf16x8 bv1 = load_frag_rowmajor(v, kn0 + 16 * n, 1, lane, HS);
-          f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              qf[mh][0], bk0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              qf[mh][1], bk1, s, 0, 0, 0);
-          f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              dof[mh][0], bv0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              dof[mh][1], bv1, dp, 0, 0, 0);
-          #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int qrow = wrow0 + mh * 16 + (lane >> 4) * 4 + r;
-            const int key = kn0 + 16 * n + col0;
-            const bool valid = key <= qrow;
-            const float p = valid
-                ? exp2f((scale * s[r] - lse_r[mh][r]) * l2e) : 0.f;
-            const float ds = valid
-                ? scale * p * (dp[r] - d_r[mh][r]) : 0.f;
-            dsw[(mh * 16 + (lane >> 4) * 4 + r) * BN + 16 * n + col0] =
-                (__bf16)ds;
-          }
-        }
-      }
-      wait_lds();
-      // dQ += dS K (K^T image)
-      #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 dsa[2];
-        #pragma unroll
-        for (int mh = 0; mh < 2; ++mh)
-          *reinterpret_cast<int4*>(&dsa[mh]) =
-              *reinterpret_cast<const int4*>(
-                  dsw + (mh * 16 + (lane & 15)) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-        #pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          bf16x8 bk;
-          *reinterpret_cast<int4*>(&bk) =
-              *reinterpret_cast<const int4*>(
-                  lds_kt + (16 * n + col0) * BN + kk * 32 +
-                  (lane >> 4) * 8);
-          #pragma unroll
-          for (int mh = 0; mh < 2; ++mh)
-            dq_acc[mh][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                dsa[mh], bk, dq_acc[mh][n], 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();
-  }
-
-  #pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qrow = wrow0 + mh * 16 + (lane >> 4) * 4 + r;
-      #pragma unroll
-      for (int n = 0; n < 4; ++n)
-        dQ[base + (long)qrow * HS + 16 * n + col0] =
-            __float2bfloat16(dq_acc[mh][n][r]);
-    }
-}
-
-}  // namespace
-
-std::vector<torch::Tensor> flash_attn_bwd(
-    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
-    torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale) {
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
-  dout = dout.contiguous();
-  auto dq = torch::empty_like(q);
-  auto dk = torch::empty_like(k);
-  auto dv = torch::empty_like(v);
-  auto D = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  const long total_rows = (long)B * H * T;
-  hipLaunchKernelGGL(flash_bwd_pre_kernel,
-                     dim3((total_rows + 63) / 64), dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
-                     D.data_ptr<float>(), total_rows);
-  dim3 grid(T / BM, B * H);
-  hipLaunchKernelGGL(flash_bwd_dkv_kernel, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     lse.data_ptr<float>(), D.data_ptr<float>(),
-                     reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-                     reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
-                     T, (float)scale);
-  hipLaunchKernelGGL(flash_bwd_dq_kernel, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     lse.data_ptr<float>(), D.data_ptr<float>(),
-                     reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
-                     T, (float)scale);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "flash_bwd: ", hipGetErrorString(e));
-  return {dq, dk, dv};
-}
-
 // =====================================================================
 // forward v3 — swapped-operand S^T design (profiles/r01_flash_attn_notes
 // round-2 plan; guide T12 structure adapted to the verified 16x16x32
 // fragment maps):
 //   S^T = mfma(K, Q^T): C gives each lane 16 kv entries of ONE q column
 //   -> softmax over kv is lane-local + 2 cross-lane combines (vs 64
-//   shfl per tile in v2), and P^T feeds the PV B-operand after an
-//   in-register redistribution (no P LDS round-trip, no extra barrier).
+//   shfl per tile in the r01 design), and P^T feeds the PV B-operand
+//   after an in-register redistribution (no P LDS round-trip, no extra
+//   barrier).
 // Per workgroup: 64 q rows, 4 waves x 16 q columns; KV tiles of 64.
 // =====================================================================
-namespace {
-
-constexpr int WQ = 16;     // q columns per wave (v3)
-constexpr int BM3 = 64;    // q rows per workgroup (v3)
+constexpr int WQ = 16;     // q columns per wave
+constexpr int BM3 = 64;    // q rows per workgroup
 
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
   union { unsigned u; __bf16 h[2]; } t;
@@ -1100,116 +491,38 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
         m_i * scale + logf(fmaxf(l_i, 1e-30f));
 }
 
-}  // namespace
-
-std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
-                                             torch::Tensor k,
-                                             torch::Tensor v,
-                                             double scale,
-                                             bool use_permlane) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
-              q.is_contiguous() && k.is_contiguous() &&
-              v.is_contiguous(), "flash_attn_fwd_v3: bf16 contiguous");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == HS,
-              "flash_attn_fwd_v3: [B,H,T,64] expected");
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
-  TORCH_CHECK(T % BM3 == 0, "flash_attn_fwd_v3: T % 64 == 0");
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  dim3 grid(T / BM3, B * H);
-  auto* kern = use_permlane ? flash_fwd_v3_kernel<true>
-                            : flash_fwd_v3_kernel<false>;
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<__hip_bfloat16*>(o.data_ptr()),
-                     lse.data_ptr<float>(), T, (float)scale, DropArgs{});
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "flash_fwd_v3: ", hipGetErrorString(e));
-  return {o, lse};
-}
-
-namespace {
-
-// Shape/dtype/device rules of the dropout entry points: the v3 kernels
-// index every operand with q's extents, so every operand must have them.
-void check_flash_dropout_operand(const torch::Tensor& t,
-                                 const torch::Tensor& q,
-                                 const char* what) {
-  TORCH_CHECK(t.sizes() == q.sizes() &&
-                  t.scalar_type() == q.scalar_type() &&
-                  t.device() == q.device() && t.is_contiguous(),
-              "flash_attn_v3_dropout: ", what,
-              " must be contiguous with q's sizes, dtype and device");
-}
-
-void check_flash_dropout_q(const torch::Tensor& q, double p) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
-                  q.is_contiguous(),
-              "flash_attn_v3_dropout: bf16 contiguous GPU tensors");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == HS,
-              "flash_attn_v3_dropout: [B,H,T,64] expected");
-  TORCH_CHECK(q.size(2) % BM3 == 0 && q.size(2) > 0,
-              "flash_attn_v3_dropout: T % 64 == 0");
-  TORCH_CHECK(q.size(0) * q.size(1) <= 65535,
-              "flash_attn_v3_dropout: B*H > 65535");
-  TORCH_CHECK(p >= 0.0 && p < 1.0,
-              "flash_attn_v3_dropout: p must be in [0, 1)");
-}
-
-}  // namespace
-
-// Forward with dropout on the attention probabilities. Draws (seed,
-// offset) from the default generator of q's device, exactly as
-// fused_dropout_ln_fwd does, and returns (o, lse, seed, offset); lse is
-// that of the undropped softmax.
-std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
-flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
-                          torch::Tensor v, double scale, double p,
-                          bool use_permlane) {
-  check_flash_dropout_q(q, p);
-  check_flash_dropout_operand(k, q, "k");
-  check_flash_dropout_operand(v, q, "v");
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
-  // graph-capture-safe RNG (device-side offset) is not implemented
-  at::cuda::assertNotCapturing(
-      "flash_attn_v3_dropout: drawing the dropout seed");
-  std::pair<uint64_t, uint64_t> rng;
-  {
-    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
-        c10::nullopt,
-        at::cuda::detail::getDefaultCUDAGenerator(q.get_device()));
-    std::lock_guard<std::mutex> lock(gen->mutex_);
-    rng = gen->philox_engine_inputs(4);
-  }
-  const DropArgs drop = make_drop_args(p, rng.first, rng.second);
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  dim3 grid(T / BM3, B * H);
-  auto* kern = use_permlane ? flash_fwd_v3_kernel<true, true>
-                            : flash_fwd_v3_kernel<false, true>;
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<__hip_bfloat16*>(o.data_ptr()),
-                     lse.data_ptr<float>(), T, (float)scale, drop);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "flash_fwd_v3_dropout: ",
-              hipGetErrorString(e));
-  return {o, lse, rng.first, rng.second};
-}
-
 // =====================================================================
 // backward v3 — same swapped-C-layout + in-register redistribution
 // structure as fwd v3 (no P^T/dS^T LDS round-trips, no per-element
 // softmax shuffles; lse/D land lane-resident where the layout allows).
 // =====================================================================
-namespace {
 
+// D = rowsum(dO * O), fp32 (shared by the DROPOUT instantiations: O
+// already carries the mask)
+__global__ __launch_bounds__(256) void flash_bwd_pre_kernel(
+    const __hip_bfloat16* __restrict__ dO,
+    const __hip_bfloat16* __restrict__ O, float* __restrict__ D,
+    long total_rows) {
+  const long row = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
+  if (row >= total_rows) return;
+  const int c0 = (threadIdx.x & 3) * 16;
+  float s = 0.f;
+  #pragma unroll
+  for (int c = 0; c < 16; c += 8) {
+    bf16x8 a, b;
+    *reinterpret_cast<int4*>(&a) = *reinterpret_cast<const int4*>(
+        dO + row * HS + c0 + c);
+    *reinterpret_cast<int4*>(&b) = *reinterpret_cast<const int4*>(
+        O + row * HS + c0 + c);
+    #pragma unroll
+    for (int i = 0; i < 8; ++i)
+      s += (float)a[i] * (float)b[i];
+  }
+  #pragma unroll
+  for (int w = 1; w <= 2; w <<= 1)
+    s += __shfl_xor(s, w, 64);
+  if ((threadIdx.x & 3) == 0) D[row] = s;
+}
 
 // Batched variant for dkv: TWO 16-row blocks' transposed fragments
 // from two images with ONE lgkm drain (half the drains of per-n
@@ -1710,15 +1023,94 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
       dQ + base + (long)(q0 + erow) * HS + ec0 + 8) = t1;
 }
 
-}  // namespace
+// =====================================================================
+// host side: one set of operand checks, one launcher per direction
+// =====================================================================
 
-std::vector<torch::Tensor> flash_attn_bwd_v3(
-    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
-    torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
-    bool use_permlane) {
+// The kernels index every operand with q's extents, so every operand
+// must have them; blockIdx.y carries B*H. p is the dropout entry points'
+// probability (the p = 0 entry points pass 0), checked right after q.
+void check_flash_q(const torch::Tensor& q, double p) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
+                  q.is_contiguous(),
+              "flash_attn_v3: bf16 contiguous GPU tensors");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == HS,
+              "flash_attn_v3: [B,H,T,64] expected");
+  TORCH_CHECK(q.size(2) % BM3 == 0 && q.size(2) > 0,
+              "flash_attn_v3: T % 64 == 0");
+  TORCH_CHECK(q.size(0) * q.size(1) <= 65535,
+              "flash_attn_v3: B*H > 65535");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "flash_attn_v3: p must be in [0, 1)");
+}
+
+void check_flash_operand(const torch::Tensor& t, const torch::Tensor& q,
+                         const char* what) {
+  TORCH_CHECK(t.sizes() == q.sizes() &&
+                  t.scalar_type() == q.scalar_type() &&
+                  t.device() == q.device() && t.is_contiguous(),
+              "flash_attn_v3: ", what,
+              " must be contiguous with q's sizes, dtype and device");
+}
+
+void check_flash_fwd(const torch::Tensor& q, const torch::Tensor& k,
+                     const torch::Tensor& v, double p = 0.0) {
+  check_flash_q(q, p);
+  check_flash_operand(k, q, "k");
+  check_flash_operand(v, q, "v");
+}
+
+// dout is the caller's dout.contiguous()
+void check_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q,
+                     const torch::Tensor& k, const torch::Tensor& v,
+                     const torch::Tensor& o, const torch::Tensor& lse,
+                     double p = 0.0) {
+  check_flash_fwd(q, k, v, p);
+  check_flash_operand(o, q, "o");
+  check_flash_operand(dout, q, "dout");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.device() == q.device() &&
+                  lse.numel() == q.size(0) * q.size(1) * q.size(2),
+              "flash_attn_v3: lse must be fp32 [B,H,T] on q's device");
+}
+
+const __hip_bfloat16* bf16_in(const torch::Tensor& t) {
+  return reinterpret_cast<const __hip_bfloat16*>(t.data_ptr());
+}
+__hip_bfloat16* bf16_out(torch::Tensor& t) {
+  return reinterpret_cast<__hip_bfloat16*>(t.data_ptr());
+}
+
+// Operands are already checked. Returns (o, lse); with dropout, lse is
+// that of the undropped softmax.
+std::pair<torch::Tensor, torch::Tensor> launch_flash_fwd(
+    const torch::Tensor& q, const torch::Tensor& k,
+    const torch::Tensor& v, double scale, const DropArgs& drop,
+    bool dropout, bool use_permlane) {
   const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
-  TORCH_CHECK(T % BM3 == 0, "flash_attn_bwd_v3: T % 64 == 0");
-  dout = dout.contiguous();
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  dim3 grid(T / BM3, B * H);
+  auto* kern =
+      dropout ? (use_permlane ? flash_fwd_v3_kernel<true, true>
+                              : flash_fwd_v3_kernel<false, true>)
+              : (use_permlane ? flash_fwd_v3_kernel<true, false>
+                              : flash_fwd_v3_kernel<false, false>);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_in(q),
+                     bf16_in(k), bf16_in(v), bf16_out(o),
+                     lse.data_ptr<float>(), T, (float)scale, drop);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "flash_fwd_v3: ", hipGetErrorString(e));
+  return {o, lse};
+}
+
+// Operands are already checked. D = rowsum(dO o O), then dK/dV, then dQ.
+std::vector<torch::Tensor> launch_flash_bwd(
+    const torch::Tensor& dout, const torch::Tensor& q,
+    const torch::Tensor& k, const torch::Tensor& v,
+    const torch::Tensor& o, const torch::Tensor& lse, double scale,
+    const DropArgs& drop, bool dropout, bool use_permlane) {
+  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
@@ -1727,93 +1119,91 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
   const long total_rows = (long)B * H * T;
   hipLaunchKernelGGL(flash_bwd_pre_kernel,
                      dim3((total_rows + 63) / 64), dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
-                     D.data_ptr<float>(), total_rows);
+                     bf16_in(dout), bf16_in(o), D.data_ptr<float>(),
+                     total_rows);
   dim3 grid(T / BM3, B * H);
-  auto* kdkv = use_permlane ? flash_bwd_dkv_v3_kernel<true>
-                            : flash_bwd_dkv_v3_kernel<false>;
-  auto* kdq = use_permlane ? flash_bwd_dq_v3_kernel<true>
-                           : flash_bwd_dq_v3_kernel<false>;
-  hipLaunchKernelGGL(kdkv, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+  auto* kdkv =
+      dropout ? (use_permlane ? flash_bwd_dkv_v3_kernel<true, true>
+                              : flash_bwd_dkv_v3_kernel<false, true>)
+              : (use_permlane ? flash_bwd_dkv_v3_kernel<true, false>
+                              : flash_bwd_dkv_v3_kernel<false, false>);
+  auto* kdq =
+      dropout ? (use_permlane ? flash_bwd_dq_v3_kernel<true, true>
+                              : flash_bwd_dq_v3_kernel<false, true>)
+              : (use_permlane ? flash_bwd_dq_v3_kernel<true, false>
+                              : flash_bwd_dq_v3_kernel<false, false>);
+  hipLaunchKernelGGL(kdkv, grid, dim3(256), 0, stream, bf16_in(q),
+                     bf16_in(k), bf16_in(v), bf16_in(dout),
                      lse.data_ptr<float>(), D.data_ptr<float>(),
-                     reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-                     reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
-                     T, (float)scale, DropArgs{});
-  hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
+                     bf16_out(dk), bf16_out(dv), T, (float)scale, drop);
+  hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream, bf16_in(q),
+                     bf16_in(k), bf16_in(v), bf16_in(dout),
                      lse.data_ptr<float>(), D.data_ptr<float>(),
-                     reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
-                     T, (float)scale, DropArgs{});
+                     bf16_out(dq), T, (float)scale, drop);
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "flash_bwd_v3: ", hipGetErrorString(e));
   return {dq, dk, dv};
 }
 
+}  // namespace
+
+std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
+                                             torch::Tensor k,
+                                             torch::Tensor v,
+                                             double scale,
+                                             bool use_permlane) {
+  check_flash_fwd(q, k, v);
+  auto [o, lse] = launch_flash_fwd(q, k, v, scale, DropArgs{}, false,
+                                   use_permlane);
+  return {o, lse};
+}
+
+std::vector<torch::Tensor> flash_attn_bwd_v3(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
+    bool use_permlane) {
+  dout = dout.contiguous();
+  check_flash_bwd(dout, q, k, v, o, lse);
+  return launch_flash_bwd(dout, q, k, v, o, lse, scale, DropArgs{},
+                          false, use_permlane);
+}
+
+// Forward with dropout on the attention probabilities. Draws (seed,
+// offset) from the default generator of q's device, exactly as
+// fused_dropout_ln_fwd does, and returns (o, lse, seed, offset).
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
+                          torch::Tensor v, double scale, double p,
+                          bool use_permlane) {
+  check_flash_fwd(q, k, v, p);
+  // graph-capture-safe RNG (device-side offset) is not implemented
+  at::cuda::assertNotCapturing(
+      "flash_attn_v3_dropout: drawing the dropout seed");
+  std::pair<uint64_t, uint64_t> rng;
+  {
+    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
+        c10::nullopt,
+        at::cuda::detail::getDefaultCUDAGenerator(q.get_device()));
+    std::lock_guard<std::mutex> lock(gen->mutex_);
+    rng = gen->philox_engine_inputs(4);
+  }
+  auto [o, lse] = launch_flash_fwd(
+      q, k, v, scale, make_drop_args(p, rng.first, rng.second), true,
+      use_permlane);
+  return {o, lse, rng.first, rng.second};
+}
+
 // Backward of flash_attn_fwd_v3_dropout: the mask is drawn again from
-// the (seed, offset) the forward returned. D = rowsum(dO o O) is the
-// dropout-free expression (O already carries the mask), so the pre
-// kernel is shared.
+// the (seed, offset) the forward returned.
 std::vector<torch::Tensor> flash_attn_bwd_v3_dropout(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
     double p, uint64_t seed, uint64_t offset, bool use_permlane) {
-  check_flash_dropout_q(q, p);
   dout = dout.contiguous();
-  check_flash_dropout_operand(k, q, "k");
-  check_flash_dropout_operand(v, q, "v");
-  check_flash_dropout_operand(o, q, "o");
-  check_flash_dropout_operand(dout, q, "dout");
-  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
-                  lse.device() == q.device() &&
-                  lse.numel() == (int64_t)B * H * T,
-              "flash_attn_v3_dropout: lse must be fp32 [B,H,T] on q's "
-              "device");
-  const DropArgs drop = make_drop_args(p, seed, offset);
-  auto dq = torch::empty_like(q);
-  auto dk = torch::empty_like(k);
-  auto dv = torch::empty_like(v);
-  auto D = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  const long total_rows = (long)B * H * T;
-  hipLaunchKernelGGL(flash_bwd_pre_kernel,
-                     dim3((total_rows + 63) / 64), dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(o.data_ptr()),
-                     D.data_ptr<float>(), total_rows);
-  dim3 grid(T / BM3, B * H);
-  auto* kdkv = use_permlane ? flash_bwd_dkv_v3_kernel<true, true>
-                            : flash_bwd_dkv_v3_kernel<false, true>;
-  auto* kdq = use_permlane ? flash_bwd_dq_v3_kernel<true, true>
-                           : flash_bwd_dq_v3_kernel<false, true>;
-  hipLaunchKernelGGL(kdkv, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     lse.data_ptr<float>(), D.data_ptr<float>(),
-                     reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-                     reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
-                     T, (float)scale, drop);
-  hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr()),
-                     lse.data_ptr<float>(), D.data_ptr<float>(),
-                     reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
-                     T, (float)scale, drop);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "flash_bwd_v3_dropout: ", hipGetErrorString(e));
-  return {dq, dk, dv};
+  check_flash_bwd(dout, q, k, v, o, lse, p);
+  return launch_flash_bwd(dout, q, k, v, o, lse, scale,
+                          make_drop_args(p, seed, offset), true,
+                          use_permlane);
 }
 
 // =====================================================================

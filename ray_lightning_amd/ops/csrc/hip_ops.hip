@@ -997,12 +997,6 @@ std::vector<torch::Tensor> fused_bn_dual_bwd(
     torch::Tensor gammad);
 
 // flash attention (causal, hs=64) — defined in flash_attn.hip
-std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q,
-                                          torch::Tensor k,
-                                          torch::Tensor v, double scale);
-std::vector<torch::Tensor> flash_attn_bwd(
-    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
-    torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale);
 std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
                                              torch::Tensor k,
                                              torch::Tensor v,
@@ -1022,17 +1016,15 @@ std::vector<torch::Tensor> flash_attn_bwd_v3_dropout(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
     double p, uint64_t seed, uint64_t offset, bool use_permlane);
-torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
-torch::Tensor perm_probe(torch::Tensor M, torch::Tensor B,
-                         long variant);
-std::vector<torch::Tensor> perm_dump(torch::Tensor M, long variant);
-torch::Tensor permlane_swap_probe();
-torch::Tensor tr16_probe(long a, long b, long c);
-torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor B);
 std::vector<torch::Tensor> flash_attn_fwd_v4(torch::Tensor q,
                                              torch::Tensor k,
                                              torch::Tensor v,
                                              double scale);
+// layout / instruction-semantics probes — defined in mfma_probe.hip
+torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
+torch::Tensor permlane_swap_probe();
+torch::Tensor tr16_probe(long a, long b, long c);
+torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor B);
 
 // fused residual-add + LayerNorm — defined in fused_ln.hip
 std::vector<torch::Tensor> fused_ln_fwd(
@@ -1174,12 +1166,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused dropout + residual-add + LayerNorm forward");
   m.def("fused_dropout_ln_bwd", &fused_dropout_ln_bwd,
         "fused dropout + residual-add + LayerNorm backward");
-  m.def("flash_attn_fwd", &flash_attn_fwd,
-        "causal flash attention forward (hs=64, bf16, MFMA)");
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3,
         "swapped-operand MFMA flash attention fwd (v3)");
-  m.def("flash_attn_bwd", &flash_attn_bwd,
-        "causal flash attention backward");
   m.def("flash_attn_bwd_v3", &flash_attn_bwd_v3,
         "swapped-operand MFMA flash attention bwd (v3)");
   m.def("flash_attn_fwd_v3_dropout", &flash_attn_fwd_v3_dropout,
@@ -1187,9 +1175,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd_v3_dropout", &flash_attn_bwd_v3_dropout,
         "v3 flash attention bwd with attention dropout");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
-  m.def("perm_probe", &perm_probe,
-        "C-layout -> A-fragment bpermute redistribution probe");
-  m.def("perm_dump", &perm_dump, "redistribution element dump");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");
   m.def("mfma_probe32", &mfma_probe32,

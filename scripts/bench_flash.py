@@ -32,16 +32,13 @@ def t(fn, n=20):
     return (time.perf_counter() - t0) / n * 1e3
 
 
-o, lse = ext.flash_attn_fwd(q, k, v, scale)
-t_fwd = t(lambda: ext.flash_attn_fwd(q, k, v, scale))
+o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, True)
 t_fwd3s = t(lambda: ext.flash_attn_fwd_v3(q, k, v, scale, False))
 t_fwd3p = t(lambda: ext.flash_attn_fwd_v3(q, k, v, scale, True))
 t_fwd4 = t(lambda: ext.flash_attn_fwd_v4(q, k, v, scale))
 print(f"fwd v3(shfl) {t_fwd3s:.3f} ms   fwd v3(permlane) {t_fwd3p:.3f} ms   fwd v4(32x32) {t_fwd4:.3f} ms")
-t_bwd = t(lambda: ext.flash_attn_bwd(dy, q, k, v, o, lse, scale))
 t_bwd3s = t(lambda: ext.flash_attn_bwd_v3(dy, q, k, v, o, lse, scale, False))
 t_bwd3p = t(lambda: ext.flash_attn_bwd_v3(dy, q, k, v, o, lse, scale, True))
-print(f"fwd {t_fwd:.3f} ms   bwd(all3) {t_bwd:.3f} ms")
 print(f"bwd v3(shfl) {t_bwd3s:.3f} ms   bwd v3(permlane) {t_bwd3p:.3f} ms")
 
 # SDPA split

@@ -22,8 +22,6 @@ which = os.environ.get("RLA_WHICH", "bwd3")
 for _ in range(30):
     if which == "bwd3":
         ext.flash_attn_bwd_v3(dy, q, k, v, o, lse, scale, True)
-    elif which == "bwd2":
-        ext.flash_attn_bwd(dy, q, k, v, o, lse, scale)
     elif which == "fwd3":
         ext.flash_attn_fwd_v3(q, k, v, scale, True)
     elif which == "fwd4":

@@ -329,6 +329,24 @@ def test_ext_entry_points_check_their_operands():
         ext.flash_attn_bwd_v3_dropout(dy[:, :, :32], q, k, v, o, lse,
                                       SCALE, 0.1, seed, off, True)
 
+    # the p = 0 entry points share the checks. Every bad operand is
+    # larger than the good one would be.
+    with pytest.raises(RuntimeError):
+        ext.flash_attn_fwd_v3(q, k2, v, SCALE, True)
+    with pytest.raises(RuntimeError):
+        ext.flash_attn_fwd_v3(q, k, v.float(), SCALE, True)
+    o, lse = ext.flash_attn_fwd_v3(q, k, v, SCALE, True)
+    o2, dy2 = torch.zeros_like(k2), torch.zeros_like(k2)
+    for bad in (dict(k=k2), dict(v=v.float()), dict(o=o2), dict(dout=dy2),
+                dict(lse=torch.cat([lse, lse])), dict(lse=lse.double())):
+        a = dict(dout=dy, q=q, k=k, v=v, o=o, lse=lse)
+        a.update(bad)
+        with pytest.raises(RuntimeError):
+            ext.flash_attn_bwd_v3(a["dout"], a["q"], a["k"], a["v"],
+                                  a["o"], a["lse"], SCALE, True)
+    # and the good operands pass
+    ext.flash_attn_bwd_v3(dy, q, k, v, o, lse, SCALE, True)
+
 
 # ------------------------------------------------------------ 8. GPT-2
 def _gpt2(attn_pdrop):

@@ -44,29 +44,6 @@ def _ref_attention(q, k, v, scale):
     return p @ v.float()
 
 
-@pytest.mark.parametrize("B,H,T", [(2, 3, 256), (1, 2, 1024), (1, 1, 128)])
-def test_flash_fwd_numerics(B, H, T):
-    from ray_lightning_amd import ops
-    ext = ops._load_ext()
-    torch.manual_seed(0)
-    hs = 64
-    q = (torch.randn(B, H, T, hs, device="cuda") * 0.5).bfloat16()
-    k = (torch.randn(B, H, T, hs, device="cuda") * 0.5).bfloat16()
-    v = (torch.randn(B, H, T, hs, device="cuda") * 0.5).bfloat16()
-    scale = 1.0 / math.sqrt(hs)
-    o, lse = ext.flash_attn_fwd(q, k, v, scale)
-    ref = _ref_attention(q, k, v, scale)
-    assert torch.allclose(o.float(), ref, atol=3e-2, rtol=3e-2), \
-        f"max err {(o.float() - ref).abs().max()}"
-    # LSE check
-    s = (q.float() @ k.float().transpose(-1, -2)) * scale
-    mask = torch.tril(torch.ones(T, T, device=q.device,
-                                 dtype=torch.bool))
-    s = s.masked_fill(~mask, float("-inf"))
-    ref_lse = torch.logsumexp(s, dim=-1)
-    assert torch.allclose(lse, ref_lse, atol=2e-2, rtol=2e-2)
-
-
 def test_flash_bwd_numerics():
     from ray_lightning_amd.ops.flash_attn import flash_attention
     torch.manual_seed(1)
@@ -130,31 +107,6 @@ def test_flash_vs_sdpa_speed():
     assert t_custom < t_sdpa * 1.15
 
 
-@pytest.mark.xfail(reason="single-bpermute-per-pair scheme is "
-                   "structurally incomplete: a source lane contributes "
-                   "one register per ds_bpermute but targets need "
-                   "lane-varying (q,n) registers — see "
-                   "profiles/r01_flash_attn_notes.md round-2 design",
-                   strict=False)
-def test_perm_redistribution_probe():
-    """C-layout -> A-fragment in-register redistribution probe (the
-    primitive the round-2 flash redesign needs instead of the P LDS
-    round-trip). Currently xfail: records the measured state and the
-    confirmed v_perm_b32 byte-pool order."""
-    from ray_lightning_amd import ops
-    ext = ops._load_ext()
-    torch.manual_seed(3)
-    M = torch.randn(16, 64, device="cuda") * 0.5
-    B = (torch.randn(64, 16, device="cuda") * 0.5).bfloat16()
-    ref = M.bfloat16().float() @ B.float()
-    errs = []
-    for variant in (0, 1):
-        C2 = ext.perm_probe(M, B, variant)
-        errs.append(float((C2 - ref).abs().max()))
-    print(f"\n[perm_probe] variant errs: {errs}")
-    assert min(errs) < 3e-2, f"neither perm variant matches: {errs}"
-
-
 @pytest.mark.parametrize("use_permlane", [False, True])
 @pytest.mark.parametrize("B,H,T", [(2, 3, 256), (1, 2, 1024),
                                    (1, 1, 64), (1, 2, 2048)])
@@ -183,17 +135,33 @@ def test_flash_fwd_v3_numerics(B, H, T, use_permlane):
         f"LSE max err {(lse - lse_ref).abs().max()}"
 
 
-def test_flash_fwd_v3_matches_v2_lse():
+def test_flash_fwd_v3_unscaled_inputs():
+    """Unit-variance q, k, v (scores ~4x those of the numerics test)
+    against the fp32 reference: the permlane build, which training
+    runs, and the bpermute build, which the test used before its rename.
+    Measured on MI355X (profiles/flash_attn_single_path.md), the same
+    for both builds: lse max abs err 9.5e-7, o max abs err 7.7e-3,
+    largest |err| / (2e-2 + 2e-2 |ref|) 0.12."""
     from ray_lightning_amd import ops
     ext = ops._load_ext()
     torch.manual_seed(1)
     q = (torch.randn(2, 2, 512, 64, device="cuda")).bfloat16()
     k = torch.randn_like(q).bfloat16()
     v = torch.randn_like(q).bfloat16()
-    o2, lse2 = ext.flash_attn_fwd(q, k, v, 0.125)
-    o3, lse3 = ext.flash_attn_fwd_v3(q, k, v, 0.125, False)
-    assert torch.allclose(lse2, lse3, atol=2e-3, rtol=1e-3)
-    assert torch.allclose(o2.float(), o3.float(), atol=2e-2, rtol=2e-2)
+    ref = _ref_attention(q, k, v, 0.125)
+    s = (q.float() @ k.float().transpose(-1, -2)) * 0.125
+    mask = torch.tril(
+        torch.ones(512, 512, device=q.device, dtype=torch.bool))
+    lse_ref = torch.logsumexp(s.masked_fill(~mask, float("-inf")), dim=-1)
+    for use_permlane in (True, False):
+        o, lse = ext.flash_attn_fwd_v3(q, k, v, 0.125, use_permlane)
+        o_err = (o.float() - ref).abs()
+        print(f"\n[flash v3 unscaled, permlane={use_permlane}] lse max err "
+              f"{(lse - lse_ref).abs().max().item():.3e}  o max err "
+              f"{o_err.max().item():.3e}  o max err/bound "
+              f"{(o_err / (2e-2 + 2e-2 * ref.abs())).max().item():.3f}")
+        assert torch.allclose(lse, lse_ref, atol=2e-3, rtol=1e-3)
+        assert torch.allclose(o.float(), ref, atol=2e-2, rtol=2e-2)
 
 
 @pytest.mark.parametrize("use_permlane", [False, True])
