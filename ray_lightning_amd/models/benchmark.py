@@ -112,7 +112,9 @@ class GPT2LM(LightningModule):
                  weight_decay: float = 0.1, batch_size: int = 8,
                  seq_len: int = 1024, dataset_length: int = 4096,
                  bf16_weights: bool = True, embd_pdrop: float = 0.0,
-                 resid_pdrop: float = 0.0, attn_pdrop: float = 0.0):
+                 resid_pdrop: float = 0.0, attn_pdrop: float = 0.0,
+                 ignore_index: int = -100, label_smoothing: float = 0.0,
+                 z_loss: float = 0.0):
         super().__init__()
         self.save_hyperparameters()
         cfg = {
@@ -125,6 +127,9 @@ class GPT2LM(LightningModule):
         cfg.embd_pdrop = embd_pdrop
         cfg.resid_pdrop = resid_pdrop
         cfg.attn_pdrop = attn_pdrop
+        cfg.ignore_index = ignore_index
+        cfg.label_smoothing = label_smoothing
+        cfg.z_loss = z_loss
         self.model = GPT2(cfg)
         if bf16_weights:
             from .gpt2 import to_bf16_training

@@ -5,6 +5,13 @@ Own implementation sized to the published GPT-2 configs. Attention uses
 torch SDPA (AOTriton flash path on ROCm); matmuls hit hipBLASLt via
 PyTorch-ROCm. The framework-owned hot path on this model is the sharded
 gradient engine + the sharded fused-Adam HIP kernel.
+
+The training loss is the chunked LM-head cross-entropy of
+ops/chunked_ce.py: targets equal to ``cfg.ignore_index`` (-100: padding,
+masked prompts, document boundaries) are left out of the mean, and
+``cfg.label_smoothing`` / ``cfg.z_loss`` add the two usual LM loss
+regularisers. Its softmax runs in the fused_ce HIP kernels when that
+path is enabled (``RLA_FUSED_CE``, docs/CONFIG.md).
 """
 from __future__ import annotations
 
@@ -32,6 +39,12 @@ class GPT2Config:
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     attn_pdrop: float = 0.0
+    # loss (ops/chunked_ce.py): targets equal to ignore_index are left
+    # out of the mean; label smoothing and the z-loss weight
+    # (z_loss * logsumexp^2) are off by default.
+    ignore_index: int = -100
+    label_smoothing: float = 0.0
+    z_loss: float = 0.0
 
     @classmethod
     def gpt2(cls):
@@ -167,11 +180,15 @@ class GPT2(nn.Module):
         if targets is not None:
             # chunked LM-head + CE: never materializes the [B*T, V]
             # logits (ops/chunked_ce.py); identical numerics to
-            # F.cross_entropy(logits.float(), t)
+            # F.cross_entropy(logits.float(), t, ignore_index=,
+            # label_smoothing=) + z_loss * mean(logsumexp^2)
             from ..ops.chunked_ce import chunked_cross_entropy
             loss = chunked_cross_entropy(
                 x.reshape(-1, x.size(-1)), self.lm_head.weight,
-                targets.reshape(-1))
+                targets.reshape(-1),
+                ignore_index=self.cfg.ignore_index,
+                label_smoothing=self.cfg.label_smoothing,
+                z_loss=self.cfg.z_loss)
             return None, loss
         return self.lm_head(x), None
 

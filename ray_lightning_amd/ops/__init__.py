@@ -14,6 +14,8 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
 - global-norm clipping: multi-tensor sum of squares (deterministic, no
   atomics), in-place scale by a device scalar, and an optional gradient
   multiplier inside the fused optimizer kernels
+- softmax cross-entropy forward/backward over logits rows with
+  ignore_index, label smoothing and z-loss (``chunked_ce.py``)
 """
 from __future__ import annotations
 

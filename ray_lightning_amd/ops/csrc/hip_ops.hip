@@ -1046,6 +1046,16 @@ std::vector<c10::optional<torch::Tensor>> fused_dropout_ln_bwd(
     torch::Tensor mean, torch::Tensor invstd, double p, uint64_t seed,
     uint64_t offset, bool has_res);
 
+// fused softmax cross-entropy (ignore_index, label smoothing, z-loss)
+// — defined in fused_ce.hip
+std::vector<torch::Tensor> fused_ce_fwd(
+    torch::Tensor logits, torch::Tensor targets, int64_t ignore_index,
+    double label_smoothing, double z_loss);
+torch::Tensor fused_ce_bwd(
+    torch::Tensor logits, torch::Tensor lse, torch::Tensor lse_lo,
+    torch::Tensor targets, torch::Tensor gscale, int64_t ignore_index,
+    double label_smoothing, double z_loss, bool inplace);
+
 
 // ===================================================================
 // fused dGELU(tanh) + bias-gradient partials: one pass over [M, F]
@@ -1212,4 +1222,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "multi-tensor sum of squares -> 1-element fp32 tensor");
   m.def("multi_tensor_scale", &multi_tensor_scale,
         "g *= *coef for a list of tensors, coef on the device");
+  m.def("fused_ce_fwd", &fused_ce_fwd,
+        "fused cross-entropy forward -> (loss_rows, lse, lse_lo)",
+        py::arg("logits"), py::arg("targets"), py::arg("ignore_index"),
+        py::arg("label_smoothing"), py::arg("z_loss"));
+  // inplace=True writes dlogits over logits and returns that tensor
+  m.def("fused_ce_bwd", &fused_ce_bwd,
+        "fused cross-entropy backward -> dlogits",
+        py::arg("logits"), py::arg("lse"), py::arg("lse_lo"),
+        py::arg("targets"), py::arg("gscale"), py::arg("ignore_index"),
+        py::arg("label_smoothing"), py::arg("z_loss"),
+        py::arg("inplace") = false);
 }
