@@ -1170,7 +1170,7 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
 
 // Forward with dropout on the attention probabilities. Draws (seed,
 // offset) from the default generator of q's device, exactly as
-// fused_dropout_ln_fwd does, and returns (o, lse, seed, offset).
+// fused_ln_fwd does for p > 0, and returns (o, lse, seed, offset).
 std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
 flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
                           torch::Tensor v, double scale, double p,

@@ -1026,21 +1026,14 @@ torch::Tensor permlane_swap_probe();
 torch::Tensor tr16_probe(long a, long b, long c);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor B);
 
-// fused residual-add + LayerNorm — defined in fused_ln.hip
-std::vector<torch::Tensor> fused_ln_fwd(
-    torch::Tensor a, c10::optional<torch::Tensor> b,
-    torch::Tensor gamma, torch::Tensor beta, double eps);
-std::vector<torch::Tensor> fused_ln_bwd(
-    torch::Tensor dy, torch::Tensor x,
-    c10::optional<torch::Tensor> dext, torch::Tensor gamma,
-    torch::Tensor mean, torch::Tensor invstd);
-// dropout fused into the same pair, mask regenerated in backward
+// fused (dropout +) residual-add + LayerNorm, mask regenerated in
+// backward — defined in fused_ln.hip
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
            uint64_t, uint64_t>
-fused_dropout_ln_fwd(torch::Tensor sub, c10::optional<torch::Tensor> res,
-                     torch::Tensor gamma, torch::Tensor beta, double eps,
-                     double p);
-std::vector<c10::optional<torch::Tensor>> fused_dropout_ln_bwd(
+fused_ln_fwd(torch::Tensor sub, c10::optional<torch::Tensor> res,
+             torch::Tensor gamma, torch::Tensor beta, double eps,
+             double p);
+std::vector<c10::optional<torch::Tensor>> fused_ln_bwd(
     torch::Tensor dy, torch::Tensor x,
     c10::optional<torch::Tensor> dext, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor invstd, double p, uint64_t seed,
@@ -1169,13 +1162,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_bn_dual_bwd", &fused_bn_dual_bwd,
         "fused NHWC relu(BN(x3) + BN(xd)) backward");
   m.def("fused_ln_fwd", &fused_ln_fwd,
-        "fused residual-add + LayerNorm forward");
+        "fused (dropout +) residual-add + LayerNorm forward");
   m.def("fused_ln_bwd", &fused_ln_bwd,
-        "fused residual-add + LayerNorm backward");
-  m.def("fused_dropout_ln_fwd", &fused_dropout_ln_fwd,
-        "fused dropout + residual-add + LayerNorm forward");
-  m.def("fused_dropout_ln_bwd", &fused_dropout_ln_bwd,
-        "fused dropout + residual-add + LayerNorm backward");
+        "fused (dropout +) residual-add + LayerNorm backward");
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3,
         "swapped-operand MFMA flash attention fwd (v3)");
   m.def("flash_attn_bwd_v3", &flash_attn_bwd_v3,

@@ -34,7 +34,7 @@ def _ln_fusable(x: torch.Tensor, weight: torch.Tensor) -> bool:
         return False
     v = 8 if x.dtype == torch.bfloat16 else 4
     c = x.shape[-1]
-    return c % v == 0 and c // v <= 16384 and _load_ext() is not None
+    return c % v == 0 and c <= 16384 and _load_ext() is not None
 
 
 class _FusedLN(torch.autograd.Function):
@@ -44,8 +44,8 @@ class _FusedLN(torch.autograd.Function):
     def forward(ctx, x, weight, bias, eps):
         ext = _load_ext()
         x = x.contiguous()
-        y, _x_new, mean, invstd = ext.fused_ln_fwd(
-            x, None, weight, bias, eps)
+        y, _x_new, mean, invstd, _seed, _offset = ext.fused_ln_fwd(
+            x, None, weight, bias, eps, 0.0)
         ctx.save_for_backward(x, mean, invstd, weight)
         return y
 
@@ -53,46 +53,24 @@ class _FusedLN(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, invstd, weight = ctx.saved_tensors
         ext = _load_ext()
-        dx, dgamma, dbeta = ext.fused_ln_bwd(
-            dy, x, None, weight, mean, invstd)
+        _d_res, dx, dgamma, dbeta = ext.fused_ln_bwd(
+            dy, x, None, weight, mean, invstd, 0.0, 0, 0, False)
         return dx, dgamma, dbeta, None
 
 
 class _FusedAddLN(torch.autograd.Function):
-    """(residual, sub_out) -> (x_new = residual + sub_out, ln(x_new))."""
-
-    @staticmethod
-    def forward(ctx, residual, sub_out, weight, bias, eps):
-        ext = _load_ext()
-        y, x_new, mean, invstd = ext.fused_ln_fwd(
-            residual.contiguous(), sub_out.contiguous(), weight, bias,
-            eps)
-        ctx.save_for_backward(x_new, mean, invstd, weight)
-        return x_new, y
-
-    @staticmethod
-    def backward(ctx, d_xnew, dy):
-        x_new, mean, invstd, weight = ctx.saved_tensors
-        ext = _load_ext()
-        dext = d_xnew.contiguous() if d_xnew is not None else None
-        dx, dgamma, dbeta = ext.fused_ln_bwd(
-            dy, x_new, dext, weight, mean, invstd)
-        # x_new = residual + sub_out: both get the same gradient
-        return dx, dx, dgamma, dbeta, None
-
-
-class _FusedDropoutAddLN(torch.autograd.Function):
     """(sub_out, residual | None) -> (x_new, ln(x_new)) with
     ``x_new = residual + keep * sub_out / (1-p)`` (``residual`` absent:
-    ``keep * sub_out / (1-p)``). The mask is a function of the (seed,
+    ``keep * sub_out / (1-p)``; ``p == 0``: ``keep = 1`` and the
+    generator is not touched). The mask is a function of the (seed,
     offset) pair the forward kernel drew from the device's default
     generator; the pair is kept on ctx as two ints and backward draws
-    the mask again from it. Saved tensors are those of ``_FusedAddLN``."""
+    the mask again from it. Nothing mask-sized is saved."""
 
     @staticmethod
     def forward(ctx, sub_out, residual, weight, bias, eps, p):
         ext = _load_ext()
-        y, x_new, mean, invstd, seed, offset = ext.fused_dropout_ln_fwd(
+        y, x_new, mean, invstd, seed, offset = ext.fused_ln_fwd(
             sub_out.contiguous(),
             residual.contiguous() if residual is not None else None,
             weight, bias, eps, p)
@@ -106,7 +84,8 @@ class _FusedDropoutAddLN(torch.autograd.Function):
         x_new, mean, invstd, weight = ctx.saved_tensors
         ext = _load_ext()
         dext = d_xnew.contiguous() if d_xnew is not None else None
-        d_res, d_sub, dgamma, dbeta = ext.fused_dropout_ln_bwd(
+        # p == 0: d_res and d_sub are one buffer, both inputs get it
+        d_res, d_sub, dgamma, dbeta = ext.fused_ln_bwd(
             dy, x_new, dext, weight, mean, invstd, ctx.p, ctx.seed,
             ctx.offset, ctx.has_res)
         return d_sub, d_res, dgamma, dbeta, None, None
@@ -126,16 +105,15 @@ def dropout_add_layer_norm(sub_out: torch.Tensor,
     just the dropout) and ``y = layer_norm(x_new)``; returns
     ``(x_new, y)``. One HIP kernel each way on GPU. With ``p == 0`` or
     ``training=False`` it is the dropout-free op, on the dropout-free
-    kernels."""
+    instantiations of the same kernels, and ``residual=None`` returns
+    ``sub_out`` itself as ``x_new``."""
     _check_p(p)
     drop = p > 0.0 and training
     if _ln_fusable(sub_out, weight):
-        if drop:
-            return _FusedDropoutAddLN.apply(sub_out, residual, weight,
-                                            bias, eps, p)
-        if residual is None:
+        if not drop and residual is None:
             return sub_out, _FusedLN.apply(sub_out, weight, bias, eps)
-        return _FusedAddLN.apply(residual, sub_out, weight, bias, eps)
+        return _FusedAddLN.apply(sub_out, residual, weight, bias, eps,
+                                 p if drop else 0.0)
     if drop:
         sub_out = F.dropout(sub_out, p, True)
     x_new = sub_out if residual is None else residual + sub_out
@@ -153,21 +131,11 @@ class FusedLayerNorm(nn.LayerNorm):
     def forward(self, x: torch.Tensor,
                 residual: Optional[torch.Tensor] = None,
                 dropout_p: float = 0.0):
-        if dropout_p != 0.0:
-            _check_p(dropout_p)
-            if self.training:
-                return dropout_add_layer_norm(
-                    x, residual, self.weight, self.bias, self.eps,
-                    dropout_p, True)
-            if residual is None:
-                return x, self.forward(x)
-        if _ln_fusable(x, self.weight):
-            if residual is None:
+        if residual is None and dropout_p == 0.0:
+            if _ln_fusable(x, self.weight):
                 return _FusedLN.apply(x, self.weight, self.bias,
                                       self.eps)
-            return _FusedAddLN.apply(residual, x, self.weight,
-                                     self.bias, self.eps)
-        if residual is None:
             return super().forward(x)
-        x_new = residual + x
-        return x_new, super().forward(x_new)
+        return dropout_add_layer_norm(
+            x, residual, self.weight, self.bias, self.eps, dropout_p,
+            self.training)

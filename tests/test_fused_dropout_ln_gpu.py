@@ -118,7 +118,7 @@ def _check_numerics(dtype, C, R, p, with_residual):
     close("dbeta", b.grad, b32.grad, gb)
     dropped = M == 0
     if R * C >= 1024:  # a 12-element mask may well keep everything
-        assert dropped.any() and not dropped.all()
+        assert (dropped.any() or p == 0) and not dropped.all()
     assert (sub.grad[dropped] == 0).all()
     if with_residual:
         close("d_residual", res.grad, res32.grad, tol)
@@ -137,6 +137,36 @@ def test_numerics_with_residual(dtype, C, R, p):
 @pytest.mark.parametrize("dtype,C,R", SHAPES, ids=_ids)
 def test_numerics_no_residual(dtype, C, R, p):
     _check_numerics(dtype, C, R, p, False)
+
+
+@pytest.mark.parametrize("with_residual", [True, False],
+                         ids=["residual", "no_residual"])
+@pytest.mark.parametrize("dtype,C,R", SHAPES, ids=_ids)
+def test_numerics_without_dropout(dtype, C, R, with_residual):
+    """p = 0 runs the dropout-free instantiations of the same kernels
+    over the same edge shapes; the recovered mask keeps everything."""
+    _check_numerics(dtype, C, R, 0.0, with_residual)
+
+
+def test_rng_untouched_when_nothing_is_dropped():
+    """Only a call that drops draws from the device's generator."""
+    R, C = 3, 8
+    ln = FusedLayerNorm(C).to("cuda").float()
+    x = torch.randn(R, C, device="cuda").to(BF16)
+    r = torch.randn(R, C, device="cuda").to(BF16)
+    torch.manual_seed(8)
+    before = torch.cuda.get_rng_state()
+    ln.train()
+    ln(x, residual=r, dropout_p=0)
+    ln(x, dropout_p=0)
+    assert torch.equal(torch.cuda.get_rng_state(), before)
+    ln.eval()
+    ln(x, residual=r, dropout_p=0.3)
+    ln(x, dropout_p=0.3)
+    assert torch.equal(torch.cuda.get_rng_state(), before)
+    ln.train()
+    ln(x, residual=r, dropout_p=0.3)
+    assert not torch.equal(torch.cuda.get_rng_state(), before)
 
 
 @pytest.mark.parametrize("p", [0.1, 0.5])

@@ -103,3 +103,68 @@ def test_gpt2_fused_chain_matches_eager_blocks():
         x, (256,), m.ln_f.weight, m.ln_f.bias, m.ln_f.eps)
     ref = m.lm_head(x)
     assert torch.allclose(logits, ref, atol=1e-3, rtol=1e-3)
+
+
+def test_ext_entry_points_check_their_operands():
+    """fused_ln_fwd / fused_ln_bwd are importable entry points: operands
+    the kernels cannot take raise from the host checks, before anything
+    is allocated or launched, and a valid call still works afterwards."""
+    ext = _ops._load_ext()
+    bf, R, C, eps = torch.bfloat16, 3, 8, 1e-5
+    g = torch.Generator(device="cuda").manual_seed(11)
+
+    def rows(r=R, c=C, dtype=bf):
+        return torch.randn(r, c, device="cuda", generator=g).to(dtype)
+
+    def vec(n, dtype=torch.float32):
+        return torch.rand(n, device="cuda", generator=g).add(0.5).to(dtype)
+
+    sub, res, gamma, beta = rows(), rows(), vec(C), vec(C)
+    for bad in (
+        (sub, rows(R, 16), gamma, beta, eps, 0.0),
+        (sub, rows(dtype=torch.float32), gamma, beta, eps, 0.0),
+        (rows(C, R).t(), res, gamma, beta, eps, 0.0),
+        (rows(dtype=torch.float16), None, gamma, beta, eps, 0.0),
+        (rows(R, 12), None, vec(12), vec(12), eps, 0.0),
+        (sub, res, vec(16), beta, eps, 0.0),
+        (sub, res, vec(C, bf), beta, eps, 0.0),
+        (sub, res, gamma, beta, eps, 1.0),
+    ):
+        with pytest.raises(RuntimeError):
+            ext.fused_ln_fwd(*bad)
+
+    dy, dext, mean, invstd = rows(), rows(), vec(R), vec(R)
+    half = torch.float16
+    for bad in (
+        (rows(dtype=half), rows(dtype=half), None, gamma, mean, invstd),
+        (dy, rows(C, R).t(), None, gamma, mean, invstd),
+        (dy, sub, rows(dtype=torch.float32), gamma, mean, invstd),
+        (rows(2), sub, dext, gamma, mean, invstd),
+        (dy, sub, dext, gamma, vec(2), invstd),
+        (dy, sub, dext, gamma, mean, vec(R, torch.float64)),
+        (dy, sub, dext, vec(16), mean, invstd),
+    ):
+        with pytest.raises(RuntimeError):
+            ext.fused_ln_bwd(*bad, 0.0, 0, 0, True)
+
+    y, x_new, mean, invstd, seed, offset = ext.fused_ln_fwd(
+        sub, res, gamma, beta, eps, 0.0)
+    assert (seed, offset) == (0, 0)
+    d_res, d_sub, dgamma, dbeta = ext.fused_ln_bwd(
+        dy, x_new, dext, gamma, mean, invstd, 0.0, 0, 0, True)
+
+    sub32 = sub.float().requires_grad_(True)
+    res32 = res.float().requires_grad_(True)
+    g32 = gamma.clone().requires_grad_(True)
+    b32 = beta.clone().requires_grad_(True)
+    xn32 = res32 + sub32
+    y32 = torch.nn.functional.layer_norm(xn32, (C,), g32, b32, eps)
+    torch.autograd.backward([xn32, y32], [dext.float(), dy.float()])
+    tol = dict(atol=5e-2, rtol=5e-2)
+    gb = dict(atol=5e-1, rtol=3e-2)
+    assert torch.allclose(x_new.float(), xn32, **tol)
+    assert torch.allclose(y.float(), y32, **tol)
+    assert torch.allclose(d_res.float(), res32.grad, **tol)
+    assert torch.allclose(d_sub.float(), sub32.grad, **tol)
+    assert torch.allclose(dgamma, g32.grad, **gb)
+    assert torch.allclose(dbeta, b32.grad, **gb)
