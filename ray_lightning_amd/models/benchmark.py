@@ -114,9 +114,12 @@ class GPT2LM(LightningModule):
                  bf16_weights: bool = True, embd_pdrop: float = 0.0,
                  resid_pdrop: float = 0.0, attn_pdrop: float = 0.0,
                  ignore_index: int = -100, label_smoothing: float = 0.0,
-                 z_loss: float = 0.0):
+                 z_loss: float = 0.0, doc_eos_id: Optional[int] = None):
         super().__init__()
         self.save_hyperparameters()
+        # packed rows: when set, training_step derives document ids from
+        # this EOS token and attention / positions stay within documents
+        self.doc_eos_id = doc_eos_id
         cfg = {
             "gpt2": GPT2Config.gpt2,
             "gpt2-medium": GPT2Config.gpt2_medium,
@@ -140,12 +143,16 @@ class GPT2LM(LightningModule):
         self.seq_len = seq_len
         self.dataset_length = dataset_length
 
-    def forward(self, idx, targets=None):
-        return self.model(idx, targets)
+    def forward(self, idx, targets=None, doc_ids=None):
+        return self.model(idx, targets, doc_ids)
 
     def training_step(self, batch, batch_idx):
         x, y = batch
-        _, loss = self(x, y)
+        if self.doc_eos_id is not None:
+            from .gpt2 import document_ids
+            _, loss = self(x, y, document_ids(x, self.doc_eos_id))
+        else:
+            _, loss = self(x, y)
         self.log("train_loss", loss)
         return loss
 

@@ -12,6 +12,12 @@ masked prompts, document boundaries) are left out of the mean, and
 ``cfg.label_smoothing`` / ``cfg.z_loss`` add the two usual LM loss
 regularisers. Its softmax runs in the fused_ce HIP kernels when that
 path is enabled (``RLA_FUSED_CE``, docs/CONFIG.md).
+
+Packed rows: ``GPT2.forward(idx, targets, doc_ids=...)`` keeps attention
+and positions within each document (``document_ids`` derives the ids
+from an EOS token; ops/flash_attn.py has the kernels). Masking the
+target that follows an EOS stays with the data pipeline, through
+``ignore_index``.
 """
 from __future__ import annotations
 
@@ -72,7 +78,7 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x):
+    def forward(self, x, doc_ids=None):
         B, T, C = x.shape
         qkv = self.c_attn(x)
         q, k, v = qkv.split(C, dim=2)
@@ -81,11 +87,13 @@ class CausalSelfAttention(nn.Module):
         k = k.view(B, T, self.n_head, hs).transpose(1, 2)
         v = v.view(B, T, self.n_head, hs).transpose(1, 2)
         # hand-written MFMA flash kernels when the shape qualifies
-        # (causal bf16 hs=64), attention dropout included; SDPA
+        # (causal bf16 hs=64), attention dropout and document masking
+        # (doc_ids: ids [B, T] or the doc_bounds pair) included; SDPA
         # (AOTriton) otherwise
         from ..ops.flash_attn import flash_attention
         y = flash_attention(
-            q, k, v, dropout_p=self.attn_pdrop if self.training else 0.0)
+            q, k, v, dropout_p=self.attn_pdrop if self.training else 0.0,
+            doc_ids=doc_ids)
         y = y.transpose(1, 2).contiguous().view(B, T, C)
         return self.c_proj(y)
 
@@ -119,11 +127,11 @@ class Block(nn.Module):
         self.mlp = MLP(cfg)
         self.resid_pdrop = cfg.resid_pdrop
 
-    def forward(self, x):
+    def forward(self, x, doc_ids=None):
         # standalone (unfused) path; GPT2.forward drives the fused
         # residual+LN chain across block boundaries instead
         p, tr = self.resid_pdrop, self.training
-        x = x + F.dropout(self.attn(self.ln_1(x)), p, tr)
+        x = x + F.dropout(self.attn(self.ln_1(x), doc_ids), p, tr)
         x = x + F.dropout(self.mlp(self.ln_2(x)), p, tr)
         return x
 
@@ -154,9 +162,24 @@ class GPT2(nn.Module):
             nn.init.normal_(m.weight, std=0.02)
 
     def forward(self, idx: torch.Tensor,
-                targets: Optional[torch.Tensor] = None):
+                targets: Optional[torch.Tensor] = None,
+                doc_ids: Optional[torch.Tensor] = None):
+        """``doc_ids`` (integer [B, T], e.g. from ``document_ids``) marks
+        the documents of packed rows: attention stays within a document
+        and positions restart at each document's first token, so a
+        packed document computes what it would compute alone."""
         B, T = idx.shape
         pos = torch.arange(T, device=idx.device)
+        bounds = None
+        if doc_ids is not None:
+            # once per batch; every layer gets the pair
+            from ..ops.flash_attn import doc_bounds
+            if tuple(doc_ids.shape) != (B, T):
+                raise ValueError(
+                    f"doc_ids must have idx's shape {[B, T]}, got "
+                    f"{list(doc_ids.shape)}")
+            bounds = doc_bounds(doc_ids.to(idx.device))
+            pos = pos[None, :] - bounds[0]
         x = self.wte(idx) + self.wpe(pos)
         # fused pre-norm chain: each residual add is folded into the
         # NEXT LayerNorm's forward (ops/fused_ln.py), crossing block
@@ -170,7 +193,7 @@ class GPT2(nn.Module):
         else:
             h = self.h[0].ln_1(x)
         for i, block in enumerate(self.h):
-            attn_out = block.attn(h)
+            attn_out = block.attn(h, bounds)
             x, h = block.ln_2(attn_out, residual=x, dropout_p=pr)
             mlp_out = block.mlp(h)
             next_ln = (self.h[i + 1].ln_1 if i + 1 < len(self.h)
@@ -191,6 +214,14 @@ class GPT2(nn.Module):
                 z_loss=self.cfg.z_loss)
             return None, loss
         return self.lm_head(x), None
+
+
+def document_ids(idx: torch.Tensor, eos_token_id: int) -> torch.Tensor:
+    """Document ids [B, T] of a packed token stream: the number of EOS
+    tokens strictly before each position, so an EOS token belongs to the
+    document it ends and the next token opens a new one."""
+    eos = (idx == eos_token_id).to(torch.int64)
+    return eos.cumsum(dim=1) - eos
 
 
 def to_bf16_training(model: nn.Module) -> nn.Module:

@@ -8,7 +8,10 @@
 // three v3 kernels is instantiated for DROPOUT false (p = 0, the
 // default training path) and true (Philox mask on the probabilities),
 // and for USE_PERMLANE true (what training runs) and false (the
-// ds_bpermute redistribution, RLA_FLASH_SHFL=1, debug).
+// ds_bpermute redistribution, RLA_FLASH_SHFL=1, debug), and for DOCS
+// false (causal over the whole row) and true (packed rows: causal
+// within each document, tiles wholly in another document skipped; see
+// "document masking" below).
 // All three share one structure: a workgroup owns 64 rows (4 waves x
 // 16), walks the other axis in tiles of 64 staged through
 // double-buffered XOR-swizzled LDS images (issue-early / write-late),
@@ -18,8 +21,8 @@
 // through LDS. Tiles above the causal diagonal are skipped per wave.
 //
 // Host side (after the kernels): one set of operand checks, one forward
-// and one backward launcher, and the four exported entry points
-// flash_attn_{fwd,bwd}_v3[_dropout] that ops/flash_attn.py calls.
+// and one backward launcher, and the eight exported entry points
+// flash_attn_{fwd,bwd}_v3[_docs][_dropout] that ops/flash_attn.py calls.
 //
 // Last in the file: flash_fwd_v4_kernel / flash_attn_fwd_v4, the
 // 32x32x16 forward experiment (slower than v3, forward only, not wired
@@ -274,15 +277,32 @@ __device__ __forceinline__ unsigned drop_nibble(const DropArgs& d,
          ((unsigned)(w.z >= d.thr) << 2) | ((unsigned)(w.w >= d.thr) << 3);
 }
 
-template <bool USE_PERMLANE, bool DROPOUT = false>
+// --- document masking (DOCS instantiations of the v3 kernels) ---------
+// A packed row holds several documents; q may attend kv iff
+// doc_start[b, q] <= kv <= q (doc_end[b, kv] is the mirror image the dkv
+// kernel needs). The kernels get one per-position int32 bound [B, T]
+// and H (b = bh / H). A bound is only ever (1) compared with a position
+// and (2) turned into the first / last TILE of a workgroup's loop after
+// a clamp into the range the causal loop already walks, so no value in
+// it, however wrong, moves an address outside the operands: wrong
+// bounds give wrong numbers, never a stray access. Wave-uniform bounds
+// go through readfirstlane so that they live in SGPRs.
+__device__ __forceinline__ int uniform_bound(const int* bnd, int pos) {
+  return __builtin_amdgcn_readfirstlane(bnd[pos]);
+}
+
+template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false>
 // min 4 waves/EU: keeps the allocator at <=128 regs so occupancy stays
-// at the LDS-allowed 4 waves/SIMD (131 regs would drop it to 3)
+// at the LDS-allowed 4 waves/SIMD (131 regs would drop it to 3). The
+// DOCS instantiations fit too (121-128 VGPRs, no scratch;
+// profiles/flash_attn_docs.md).
 __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
     const __hip_bfloat16* __restrict__ Q,
     const __hip_bfloat16* __restrict__ K,
     const __hip_bfloat16* __restrict__ V,
     __hip_bfloat16* __restrict__ O, float* __restrict__ LSE,
-    int T, float scale, DropArgs drop) {
+    int T, float scale, DropArgs drop,
+    const int* __restrict__ doc_start, int H) {
   const int bh = blockIdx.y;
   const int qm0 = blockIdx.x * BM3;
   if (qm0 >= T) return;
@@ -316,21 +336,37 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
 
   const float l2e = 1.4426950408889634f * scale;
   const int kv_end = (qm0 + BM3 < T) ? qm0 + BM3 : T;
-  // prologue: tile 0 staged through registers, then the loop keeps one
-  // tile in flight (issue loads -> compute current -> write other buf)
+  // DOCS: this lane's doc_start, the wave's smallest and largest (starts
+  // do not decrease with q), and the first tile of the workgroup's loop:
+  // the one that holds doc_start[qm0], clamped into [0, qm0]
+  int mystart = 0, wstart_lo = 0, wstart_hi = 0, kv_begin = 0;
+  if constexpr (DOCS) {
+    const int* ds = doc_start + (long)(bh / H) * T;
+    mystart = ds[myq];
+    wstart_lo = uniform_bound(ds, q0);
+    wstart_hi = uniform_bound(ds, q0 + WQ - 1);
+    const int s0 = uniform_bound(ds, qm0);
+    kv_begin = (s0 < 0 ? 0 : (s0 > qm0 ? qm0 : s0)) & ~(BN - 1);
+  }
+  // prologue: the first tile staged through registers, then the loop
+  // keeps one tile in flight (issue loads -> compute current -> write
+  // other buf)
   {
-    StageRegsR vt = stage_r_load(v, 0);
-    StageRegsR kt = stage_r_load(k, 0);
+    StageRegsR vt = stage_r_load(v, kv_begin);
+    StageRegsR kt = stage_r_load(k, kv_begin);
     stage_r_write(lds_v[0], vt);
     stage_r_write(lds_k[0], kt);
   }
   __syncthreads();
   int buf = 0;
-  for (int kn0 = 0; kn0 < kv_end; kn0 += BN, buf ^= 1) {
+  for (int kn0 = kv_begin; kn0 < kv_end; kn0 += BN, buf ^= 1) {
     const int next = (kn0 + BN < kv_end) ? kn0 + BN : kn0;
     StageRegsR vt = stage_r_load(v, next);
     StageRegsR kt = stage_r_load(k, next);
-    const bool active = kn0 <= q0 + WQ - 1;
+    // DOCS: a tile that ends before the wave's smallest start is dead
+    // work for the whole wave, like one above the diagonal
+    const bool active = kn0 <= q0 + WQ - 1 &&
+                        (!DOCS || kn0 + BN - 1 >= wstart_lo);
     if (active) {
       // --- S^T = K Q^T: lane gets kv = kn0+16*sub+4*g+r of column myq
       // (T5: favor the MFMA-entering wave over waves in their
@@ -367,7 +403,18 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
       }
       __builtin_amdgcn_s_setprio(0);
       // --- causal mask (only tiles overlapping the diagonal) ---------
-      if (kn0 + BN - 1 > q0) {
+      if constexpr (DOCS) {
+        // ... or holding a kv before the start of one of the wave's q
+        if (kn0 + BN - 1 > q0 || kn0 < wstart_hi) {
+          #pragma unroll
+          for (int sub = 0; sub < 4; ++sub)
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int kv = kn0 + 16 * sub + 4 * g + r;
+              if (kv > myq || kv < mystart) st[sub][r] = kNegInf;
+            }
+        }
+      } else if (kn0 + BN - 1 > q0) {
         #pragma unroll
         for (int sub = 0; sub < 4; ++sub)
           #pragma unroll
@@ -409,14 +456,36 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           // masked entries are kNegInf: the raw exp2 underflows the
-          // ~-1.8e29 exponent to exactly 0 — no guard needed (every
-          // lane's FIRST tile contains kv<=q, so m_new is finite)
+          // ~-1.8e29 exponent to exactly 0 — no guard needed (without
+          // DOCS every lane's FIRST tile contains kv<=q, so m_new is
+          // finite; with DOCS see `dead` below)
           const float p = fast_exp2((st[sub][r] - m_new) * l2e);
           st[sub][r] = p;
           rowsum += p;
         }
       rowsum += __shfl_xor(rowsum, 16, 64);
       rowsum += __shfl_xor(rowsum, 32, 64);
+      // DOCS: a lane whose whole tile lies before its doc_start (`dead`;
+      // T=128, documents [0,70) [70,128): rows 70..79 on tile 0, which
+      // their wave walks for rows 64..69) has mx = m_i = kNegInf, so
+      // m_new = kNegInf whether the wave defers or not, every p above is
+      // exp2(0) = 1 and the PV below adds 64 rows of V to its o_acc.
+      // The lane is put back to its initial state instead: rowsum 0
+      // here (corr is 1, so l_i stays 0; m_i stays kNegInf) and o_acc
+      // zeroed by a SELECT after the PV, which also holds when those V
+      // rows are Inf/NaN, where the rescale by exp2(kNegInf - m) = 0 of
+      // the lane's first live tile would not. The T13 vote cannot keep
+      // the bad maximum: the dead lane's vote is (kNegInf - kNegInf)
+      // * l2e = 0 <= 8, so it never blocks a deferral of the others,
+      // and on its first live tile (mx - kNegInf) * l2e is ~1e29 > 8,
+      // so the wave does not defer and m_new becomes the finite mx. Its
+      // p = 1 columns stay out of every other lane's result: an MFMA
+      // column depends on that column of B alone.
+      bool dead = false;
+      if constexpr (DOCS) {
+        dead = kn0 + BN - 1 < mystart;
+        rowsum = dead ? 0.f : rowsum;
+      }
       l_i = l_i * corr + rowsum;
       m_i = m_new;
       if constexpr (DROPOUT) {
@@ -458,6 +527,16 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
             va1, pb[1], o_acc[n], 0, 0, 0);
       }
       __builtin_amdgcn_s_setprio(0);
+      if constexpr (DOCS) {
+        // dead lanes back to zero (above); only tiles that have one
+        if (kn0 + BN - 1 < wstart_hi) {
+          #pragma unroll
+          for (int n = 0; n < 4; ++n)
+            #pragma unroll
+            for (int r = 0; r < 4; ++r)
+              o_acc[n][r] = dead ? 0.f : o_acc[n][r];
+        }
+      }
     }
     // write-late: next tile's regs -> the other buffers, one barrier
     stage_r_write(lds_v[buf ^ 1], vt);
@@ -595,20 +674,24 @@ __device__ __forceinline__ unsigned quad_xchg(unsigned v) {
 //   dP[q][kv]  = mfma(dO_frag, V^T B-frag)
 //   dV^T[d][kv]= mfma(dO^T A-frag(lds), redist(P) B-frag)
 //   dK^T[d][kv]= mfma(Q^T  A-frag(lds), redist(dS) B-frag)
-template <bool USE_PERMLANE, bool DROPOUT = false>
+template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false>
 // min 3 waves/EU (the LDS cap): the pair-batched tr reads push regs to
 // ~172 which rounds to 2 waves without the bound. Postmortem rule:
 // verified ScratchSize stays 0 under this bound (spills + hand asm
 // were the r02 nondeterminism bug). DROPOUT spills at 170 (44-68
-// bytes), so those instantiations take 2 waves.
-__global__ __launch_bounds__(256, DROPOUT ? 2 : 3) void flash_bwd_dkv_v3_kernel(
+// bytes), so those instantiations take 2 waves; so does DOCS in the
+// bpermute build (8 bytes at 3 waves; the permlane one fits in 168).
+__global__ __launch_bounds__(
+    256, (DROPOUT || (DOCS && !USE_PERMLANE)) ? 2 : 3)
+void flash_bwd_dkv_v3_kernel(
     const __hip_bfloat16* __restrict__ Qg,
     const __hip_bfloat16* __restrict__ Kg,
     const __hip_bfloat16* __restrict__ Vg,
     const __hip_bfloat16* __restrict__ dOg,
     const float* __restrict__ LSE, const float* __restrict__ Dg,
     __hip_bfloat16* __restrict__ dK, __hip_bfloat16* __restrict__ dV,
-    int T, float scale, DropArgs drop) {
+    int T, float scale, DropArgs drop,
+    const int* __restrict__ doc_end, int H) {
   const int bh = blockIdx.y;
   const int kb0 = blockIdx.x * BM3;      // 64 KV rows per workgroup
   if (kb0 >= T) return;
@@ -660,9 +743,21 @@ __global__ __launch_bounds__(256, DROPOUT ? 2 : 3) void flash_bwd_dkv_v3_kernel(
     }
   }
   __syncthreads();
+  // DOCS: this lane's doc_end, the wave's largest (ends do not decrease
+  // with kv), and the end of the workgroup's loop: after the tile that
+  // holds doc_end[kb0 + 63], clamped into [kb0, T - 1]
+  int myend = 0, wend_hi = 0, q_stop = T;
+  if constexpr (DOCS) {
+    const int* de = doc_end + (long)(bh / H) * T;
+    myend = de[mykv];
+    wend_hi = uniform_bound(de, kv0 + WQ - 1);
+    const int e1 = uniform_bound(de, kb0 + BM3 - 1);
+    q_stop = ((e1 < kb0 ? kb0 : (e1 > T - 1 ? T - 1 : e1)) & ~(BN - 1)) +
+             BN;
+  }
   int buf = 0;
-  for (int qm0 = kb0; qm0 < T; qm0 += BN, buf ^= 1) {
-    const int next = (qm0 + BN < T) ? qm0 + BN : qm0;
+  for (int qm0 = kb0; qm0 < q_stop; qm0 += BN, buf ^= 1) {
+    const int next = (qm0 + BN < q_stop) ? qm0 + BN : qm0;
     StageRegsR dt = stage_r_load(dO, next);
     StageRegsR qt = stage_r_load(q, next);
     float nlse = 0.f, nd = 0.f;
@@ -670,7 +765,9 @@ __global__ __launch_bounds__(256, DROPOUT ? 2 : 3) void flash_bwd_dkv_v3_kernel(
       nlse = lse[next + threadIdx.x];
       nd = Drow[next + threadIdx.x];
     }
-    const bool active = kv0 <= qm0 + BN - 1;
+    // DOCS: a q tile that begins after the wave's largest end is dead
+    // work for the whole wave
+    const bool active = kv0 <= qm0 + BN - 1 && (!DOCS || qm0 <= wend_hi);
     if (active) {
       float pv[4][4], dsv[4][4];
       #pragma unroll
@@ -722,7 +819,8 @@ __global__ __launch_bounds__(256, DROPOUT ? 2 : 3) void flash_bwd_dkv_v3_kernel(
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qi = 16 * sub + 4 * g + r;     // tile-local q
-          const bool valid = (qm0 + qi) >= mykv;
+          const bool valid = (qm0 + qi) >= mykv &&
+                             (!DOCS || (qm0 + qi) <= myend);
           // mask the EXPONENT instead of p and ds: raw exp2 of -1e30
           // is exactly 0, and ds = scale*p*(...) inherits the zero —
           // one select instead of two per element
@@ -873,7 +971,7 @@ __device__ __forceinline__ void read_frag_tr_2col(const __bf16* img,
 //   S^T[kv][q]  = mfma(K_frag,  Q^T B-frag)
 //   dP^T[kv][q] = mfma(V_frag,  dO^T B-frag)
 //   dQ^T[d][q]  = mfma(K^T A-frag(lds), redist(dS^T) B-frag)
-template <bool USE_PERMLANE, bool DROPOUT = false>
+template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false>
 // min 4 waves/EU: LDS allows 6, keep the allocator under 128 regs
 __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ Qg,
@@ -882,7 +980,7 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ dOg,
     const float* __restrict__ LSE, const float* __restrict__ Dg,
     __hip_bfloat16* __restrict__ dQ, int T, float scale,
-    DropArgs drop) {
+    DropArgs drop, const int* __restrict__ doc_start, int H) {
   const int bh = blockIdx.y;
   const int qm0 = blockIdx.x * BM3;
   if (qm0 >= T) return;
@@ -918,19 +1016,30 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
 
   const float l2e = 1.4426950408889634f;
   const int kv_end = (qm0 + BM3 < T) ? qm0 + BM3 : T;
+  // DOCS: as in the forward (no dead-lane care needed here: a masked
+  // entry's exponent is -1e30 against the finite lse_q, so its dS is 0)
+  int mystart = 0, wstart_lo = 0, kv_begin = 0;
+  if constexpr (DOCS) {
+    const int* ds = doc_start + (long)(bh / H) * T;
+    mystart = ds[myq];
+    wstart_lo = uniform_bound(ds, q0);
+    const int s0 = uniform_bound(ds, qm0);
+    kv_begin = (s0 < 0 ? 0 : (s0 > qm0 ? qm0 : s0)) & ~(BN - 1);
+  }
   {
-    StageRegsR kt = stage_r_load(k, 0);
-    StageRegsR vt = stage_r_load(v, 0);
+    StageRegsR kt = stage_r_load(k, kv_begin);
+    StageRegsR vt = stage_r_load(v, kv_begin);
     stage_r_write(lds_kk[0], kt);
     stage_r_write(lds_vv[0], vt);
   }
   __syncthreads();
   int buf = 0;
-  for (int kn0 = 0; kn0 < kv_end; kn0 += BN, buf ^= 1) {
+  for (int kn0 = kv_begin; kn0 < kv_end; kn0 += BN, buf ^= 1) {
     const int next = (kn0 + BN < kv_end) ? kn0 + BN : kn0;
     StageRegsR kt = stage_r_load(k, next);
     StageRegsR vt = stage_r_load(v, next);
-    const bool active = kn0 <= q0 + WQ - 1;
+    const bool active = kn0 <= q0 + WQ - 1 &&
+                        (!DOCS || kn0 + BN - 1 >= wstart_lo);
     if (active) {
       float dsv[4][4];
       #pragma unroll
@@ -966,7 +1075,7 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kvr = kn0 + 16 * sub + 4 * g + r;
-          const bool valid = kvr <= myq;
+          const bool valid = kvr <= myq && (!DOCS || kvr >= mystart);
           const float e = valid
               ? (scale * st[r] - lse_q) * l2e : -1e30f;
           dsv[sub][r] = scale * fast_exp2(e) * (dpt[r] - d_q);
@@ -1073,6 +1182,18 @@ void check_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q,
               "flash_attn_v3: lse must be fp32 [B,H,T] on q's device");
 }
 
+// A document bound (doc_start or doc_end) of the DOCS entry points. Only
+// its layout is checked: the kernels never index with its values (see
+// "document masking" above).
+void check_flash_bound(const torch::Tensor& t, const torch::Tensor& q,
+                       const char* what) {
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() &&
+                  t.device() == q.device() && t.dim() == 2 &&
+                  t.size(0) == q.size(0) && t.size(1) == q.size(2),
+              "flash_attn_v3: ", what,
+              " must be int32 contiguous [B,T] on q's device");
+}
+
 const __hip_bfloat16* bf16_in(const torch::Tensor& t) {
   return reinterpret_cast<const __hip_bfloat16*>(t.data_ptr());
 }
@@ -1080,36 +1201,56 @@ __hip_bfloat16* bf16_out(torch::Tensor& t) {
   return reinterpret_cast<__hip_bfloat16*>(t.data_ptr());
 }
 
+// The instantiation for (use_permlane, dropout, docs): all eight of a
+// kernel have one signature.
+#define RLA_PICK_V3(KERNEL, pl, dr, dc)                                  \
+  ((dc) ? ((dr) ? ((pl) ? KERNEL<true, true, true>                       \
+                        : KERNEL<false, true, true>)                     \
+                : ((pl) ? KERNEL<true, false, true>                      \
+                        : KERNEL<false, false, true>))                   \
+        : ((dr) ? ((pl) ? KERNEL<true, true, false>                      \
+                        : KERNEL<false, true, false>)                    \
+                : ((pl) ? KERNEL<true, false, false>                     \
+                        : KERNEL<false, false, false>)))
+
+const int* bound_ptr(const torch::Tensor* t) {
+  return t ? t->data_ptr<int>() : nullptr;
+}
+
 // Operands are already checked. Returns (o, lse); with dropout, lse is
-// that of the undropped softmax.
+// that of the undropped softmax. doc_start (checked too) selects the
+// DOCS instantiation; nullptr is plain causal attention.
 std::pair<torch::Tensor, torch::Tensor> launch_flash_fwd(
     const torch::Tensor& q, const torch::Tensor& k,
     const torch::Tensor& v, double scale, const DropArgs& drop,
-    bool dropout, bool use_permlane) {
+    bool dropout, bool use_permlane,
+    const torch::Tensor* doc_start = nullptr) {
   const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, T}, q.options().dtype(at::kFloat));
   auto stream = at::hip::getCurrentHIPStream().stream();
   dim3 grid(T / BM3, B * H);
-  auto* kern =
-      dropout ? (use_permlane ? flash_fwd_v3_kernel<true, true>
-                              : flash_fwd_v3_kernel<false, true>)
-              : (use_permlane ? flash_fwd_v3_kernel<true, false>
-                              : flash_fwd_v3_kernel<false, false>);
+  auto* kern = RLA_PICK_V3(flash_fwd_v3_kernel, use_permlane, dropout,
+                           doc_start != nullptr);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_in(q),
                      bf16_in(k), bf16_in(v), bf16_out(o),
-                     lse.data_ptr<float>(), T, (float)scale, drop);
+                     lse.data_ptr<float>(), T, (float)scale, drop,
+                     bound_ptr(doc_start), H);
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "flash_fwd_v3: ", hipGetErrorString(e));
   return {o, lse};
 }
 
 // Operands are already checked. D = rowsum(dO o O), then dK/dV, then dQ.
+// doc_start and doc_end (checked too) come together or not at all.
 std::vector<torch::Tensor> launch_flash_bwd(
     const torch::Tensor& dout, const torch::Tensor& q,
     const torch::Tensor& k, const torch::Tensor& v,
     const torch::Tensor& o, const torch::Tensor& lse, double scale,
-    const DropArgs& drop, bool dropout, bool use_permlane) {
+    const DropArgs& drop, bool dropout, bool use_permlane,
+    const torch::Tensor* doc_start = nullptr,
+    const torch::Tensor* doc_end = nullptr) {
+  const bool docs = doc_start != nullptr;
   const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
@@ -1122,24 +1263,20 @@ std::vector<torch::Tensor> launch_flash_bwd(
                      bf16_in(dout), bf16_in(o), D.data_ptr<float>(),
                      total_rows);
   dim3 grid(T / BM3, B * H);
-  auto* kdkv =
-      dropout ? (use_permlane ? flash_bwd_dkv_v3_kernel<true, true>
-                              : flash_bwd_dkv_v3_kernel<false, true>)
-              : (use_permlane ? flash_bwd_dkv_v3_kernel<true, false>
-                              : flash_bwd_dkv_v3_kernel<false, false>);
-  auto* kdq =
-      dropout ? (use_permlane ? flash_bwd_dq_v3_kernel<true, true>
-                              : flash_bwd_dq_v3_kernel<false, true>)
-              : (use_permlane ? flash_bwd_dq_v3_kernel<true, false>
-                              : flash_bwd_dq_v3_kernel<false, false>);
+  auto* kdkv = RLA_PICK_V3(flash_bwd_dkv_v3_kernel, use_permlane,
+                           dropout, docs);
+  auto* kdq = RLA_PICK_V3(flash_bwd_dq_v3_kernel, use_permlane, dropout,
+                          docs);
   hipLaunchKernelGGL(kdkv, grid, dim3(256), 0, stream, bf16_in(q),
                      bf16_in(k), bf16_in(v), bf16_in(dout),
                      lse.data_ptr<float>(), D.data_ptr<float>(),
-                     bf16_out(dk), bf16_out(dv), T, (float)scale, drop);
+                     bf16_out(dk), bf16_out(dv), T, (float)scale, drop,
+                     bound_ptr(doc_end), H);
   hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream, bf16_in(q),
                      bf16_in(k), bf16_in(v), bf16_in(dout),
                      lse.data_ptr<float>(), D.data_ptr<float>(),
-                     bf16_out(dq), T, (float)scale, drop);
+                     bf16_out(dq), T, (float)scale, drop,
+                     bound_ptr(doc_start), H);
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "flash_bwd_v3: ", hipGetErrorString(e));
   return {dq, dk, dv};
@@ -1171,11 +1308,11 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
 // Forward with dropout on the attention probabilities. Draws (seed,
 // offset) from the default generator of q's device, exactly as
 // fused_ln_fwd does for p > 0, and returns (o, lse, seed, offset).
+namespace {
 std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
-flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
-                          torch::Tensor v, double scale, double p,
-                          bool use_permlane) {
-  check_flash_fwd(q, k, v, p);
+flash_fwd_dropout(const torch::Tensor& q, const torch::Tensor& k,
+                  const torch::Tensor& v, double scale, double p,
+                  bool use_permlane, const torch::Tensor* doc_start) {
   // graph-capture-safe RNG (device-side offset) is not implemented
   at::cuda::assertNotCapturing(
       "flash_attn_v3_dropout: drawing the dropout seed");
@@ -1189,8 +1326,17 @@ flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
   }
   auto [o, lse] = launch_flash_fwd(
       q, k, v, scale, make_drop_args(p, rng.first, rng.second), true,
-      use_permlane);
+      use_permlane, doc_start);
   return {o, lse, rng.first, rng.second};
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_dropout(torch::Tensor q, torch::Tensor k,
+                          torch::Tensor v, double scale, double p,
+                          bool use_permlane) {
+  check_flash_fwd(q, k, v, p);
+  return flash_fwd_dropout(q, k, v, scale, p, use_permlane, nullptr);
 }
 
 // Backward of flash_attn_fwd_v3_dropout: the mask is drawn again from
@@ -1204,6 +1350,56 @@ std::vector<torch::Tensor> flash_attn_bwd_v3_dropout(
   return launch_flash_bwd(dout, q, k, v, o, lse, scale,
                           make_drop_args(p, seed, offset), true,
                           use_permlane);
+}
+
+// Document-masked variants (the DOCS instantiations): q attends kv iff
+// doc_start[b, q] <= kv <= q; doc_end[b, kv] is the last q that attends
+// kv. Both are int32 [B, T]; ops/flash_attn.py derives them.
+std::vector<torch::Tensor> flash_attn_fwd_v3_docs(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor doc_start, double scale, bool use_permlane) {
+  check_flash_fwd(q, k, v);
+  check_flash_bound(doc_start, q, "doc_start");
+  auto [o, lse] = launch_flash_fwd(q, k, v, scale, DropArgs{}, false,
+                                   use_permlane, &doc_start);
+  return {o, lse};
+}
+
+std::vector<torch::Tensor> flash_attn_bwd_v3_docs(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse,
+    torch::Tensor doc_start, torch::Tensor doc_end, double scale,
+    bool use_permlane) {
+  dout = dout.contiguous();
+  check_flash_bwd(dout, q, k, v, o, lse);
+  check_flash_bound(doc_start, q, "doc_start");
+  check_flash_bound(doc_end, q, "doc_end");
+  return launch_flash_bwd(dout, q, k, v, o, lse, scale, DropArgs{},
+                          false, use_permlane, &doc_start, &doc_end);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_docs_dropout(torch::Tensor q, torch::Tensor k,
+                               torch::Tensor v, torch::Tensor doc_start,
+                               double scale, double p,
+                               bool use_permlane) {
+  check_flash_fwd(q, k, v, p);
+  check_flash_bound(doc_start, q, "doc_start");
+  return flash_fwd_dropout(q, k, v, scale, p, use_permlane, &doc_start);
+}
+
+std::vector<torch::Tensor> flash_attn_bwd_v3_docs_dropout(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse,
+    torch::Tensor doc_start, torch::Tensor doc_end, double scale,
+    double p, uint64_t seed, uint64_t offset, bool use_permlane) {
+  dout = dout.contiguous();
+  check_flash_bwd(dout, q, k, v, o, lse, p);
+  check_flash_bound(doc_start, q, "doc_start");
+  check_flash_bound(doc_end, q, "doc_end");
+  return launch_flash_bwd(dout, q, k, v, o, lse, scale,
+                          make_drop_args(p, seed, offset), true,
+                          use_permlane, &doc_start, &doc_end);
 }
 
 // =====================================================================

@@ -1016,6 +1016,25 @@ std::vector<torch::Tensor> flash_attn_bwd_v3_dropout(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     torch::Tensor v, torch::Tensor o, torch::Tensor lse, double scale,
     double p, uint64_t seed, uint64_t offset, bool use_permlane);
+// v3 with document masking for packed rows (int32 [B,T] bounds)
+std::vector<torch::Tensor> flash_attn_fwd_v3_docs(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor doc_start, double scale, bool use_permlane);
+std::vector<torch::Tensor> flash_attn_bwd_v3_docs(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse,
+    torch::Tensor doc_start, torch::Tensor doc_end, double scale,
+    bool use_permlane);
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_docs_dropout(torch::Tensor q, torch::Tensor k,
+                               torch::Tensor v, torch::Tensor doc_start,
+                               double scale, double p,
+                               bool use_permlane);
+std::vector<torch::Tensor> flash_attn_bwd_v3_docs_dropout(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse,
+    torch::Tensor doc_start, torch::Tensor doc_end, double scale,
+    double p, uint64_t seed, uint64_t offset, bool use_permlane);
 std::vector<torch::Tensor> flash_attn_fwd_v4(torch::Tensor q,
                                              torch::Tensor k,
                                              torch::Tensor v,
@@ -1173,6 +1192,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "v3 flash attention fwd with attention dropout");
   m.def("flash_attn_bwd_v3_dropout", &flash_attn_bwd_v3_dropout,
         "v3 flash attention bwd with attention dropout");
+  m.def("flash_attn_fwd_v3_docs", &flash_attn_fwd_v3_docs,
+        "v3 flash attention fwd with document masking");
+  m.def("flash_attn_bwd_v3_docs", &flash_attn_bwd_v3_docs,
+        "v3 flash attention bwd with document masking");
+  m.def("flash_attn_fwd_v3_docs_dropout", &flash_attn_fwd_v3_docs_dropout,
+        "v3 flash attention fwd with document masking and dropout");
+  m.def("flash_attn_bwd_v3_docs_dropout", &flash_attn_bwd_v3_docs_dropout,
+        "v3 flash attention bwd with document masking and dropout");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");
