@@ -210,6 +210,78 @@ __global__ void bn_stats_coef_kernel(
   }
 }
 
+// --------------------------------------------------------------------
+// synchronized BN: the forward and backward above, cut where the
+// per-channel sums exist so that they can be all-reduced across ranks.
+// sums = [2C+1]: sum(x), sum(x^2), then the row count as one fp32 word
+// (summed over ranks it is off by at most 2^-24 relative, below the
+// rounding of the sums themselves). bsums = [2C]: sum(dy_eff),
+// sum(dy_eff * xhat). The kB2 rows are folded in the order of
+// bn_stats_coef_kernel / bn_bwd_coef_kernel: one rank gives their bits.
+// --------------------------------------------------------------------
+__global__ void bn_sync_fold_kernel(
+    const float* __restrict__ partial2, float* __restrict__ sums, int C,
+    float count, bool with_count) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const long b2C = (long)kB2 * C;
+  float s = 0.f, s2 = 0.f;
+  #pragma unroll
+  for (int b = 0; b < kB2; ++b) {
+    s += partial2[(long)b * C + c];
+    s2 += partial2[b2C + (long)b * C + c];
+  }
+  sums[c] = s;
+  sums[C + c] = s2;
+  if (with_count && c == 0) sums[2 * C] = count;
+}
+
+// bn_stats_coef_kernel on reduced sums, the global row count read from
+// the device
+__global__ void bn_sync_stats_coef_kernel(
+    const float* __restrict__ sums, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ running_mean,
+    float* __restrict__ running_var, float* __restrict__ mean_out,
+    float* __restrict__ invstd_out, float* __restrict__ scale_out,
+    float* __restrict__ bias_out, int C, float momentum, float eps) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float R = sums[2 * C];
+  const float m = sums[c] / R;
+  const float var = fmaxf(sums[C + c] / R - m * m, 0.f);
+  const float inv = rsqrtf(var + eps);
+  mean_out[c] = m;
+  invstd_out[c] = inv;
+  const float sc = gamma[c] * inv;
+  scale_out[c] = sc;
+  bias_out[c] = beta[c] - m * sc;
+  if (running_mean != nullptr) {
+    const float var_unb = R > 1.f ? var * R / (R - 1.f) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+    running_var[c] = (1.f - momentum) * running_var[c] +
+                     momentum * var_unb;
+  }
+}
+
+// bn_bwd_coef_kernel on reduced sums; dgamma/dbeta stay the caller's
+// local sums
+__global__ void bn_sync_bwd_coef_kernel(
+    const float* __restrict__ bsums, const float* __restrict__ count,
+    const float* __restrict__ gamma, const float* __restrict__ mean,
+    const float* __restrict__ invstd, float* __restrict__ coefP,
+    float* __restrict__ coefQ, float* __restrict__ coefS, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float dsum = bsums[c];
+  const float dxhat = bsums[C + c];
+  const float invR = 1.f / count[0];
+  const float P = gamma[c] * invstd[c];
+  const float Q = -P * invstd[c] * dxhat * invR;
+  coefP[c] = P;
+  coefQ[c] = Q;
+  coefS[c] = -P * dsum * invR - Q * mean[c];
+}
+
 // eval mode: scale/bias straight from running stats
 __global__ void bn_eval_coef_kernel(
     const float* __restrict__ running_mean,
@@ -791,17 +863,11 @@ long bn_grid_elems(long nvec) {
   return std::min<long>(std::max<long>(blocks, 1), 16384);
 }
 
-// training-mode stats -> fold -> coef: batch mean/invstd, the apply
-// pass's scale/bias, and the running-stat update
+// stats -> fold: the [2, kB2, C] second-level partials of sum / sumsq
 template <typename T>
-void bn_train_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
-                    const torch::Tensor& beta,
-                    torch::Tensor& running_mean,
-                    torch::Tensor& running_var, torch::Tensor& mean,
-                    torch::Tensor& invstd, torch::Tensor& scale,
-                    torch::Tensor& bias, double momentum, double eps,
-                    long R, int C, hipStream_t stream) {
-  auto opts = gamma.options().dtype(at::kFloat);
+torch::Tensor bn_stats_partial2(const torch::Tensor& x,
+                                const at::TensorOptions& opts, long R,
+                                int C, hipStream_t stream) {
   const int tpr = C / BnVec<T>::V;
   const int rpb = kT / tpr;
   const int nb = bn_grid_rows(R, rpb);
@@ -817,6 +883,21 @@ void bn_train_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
                      stream, partial.data_ptr<float>(), nb,
                      partial2.data_ptr<float>(), C);
   CHECK_HIP_BN(hipGetLastError());
+  return partial2;
+}
+
+// training-mode stats -> fold -> coef: batch mean/invstd, the apply
+// pass's scale/bias, and the running-stat update
+template <typename T>
+void bn_train_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
+                    const torch::Tensor& beta,
+                    torch::Tensor& running_mean,
+                    torch::Tensor& running_var, torch::Tensor& mean,
+                    torch::Tensor& invstd, torch::Tensor& scale,
+                    torch::Tensor& bias, double momentum, double eps,
+                    long R, int C, hipStream_t stream) {
+  torch::Tensor partial2 = bn_stats_partial2<T>(
+      x, gamma.options().dtype(at::kFloat), R, C, stream);
   hipLaunchKernelGGL(bn_stats_coef_kernel, dim3((C + 255) / 256),
                      dim3(256), 0, stream, partial2.data_ptr<float>(),
                      gamma.data_ptr<float>(),
@@ -828,6 +909,38 @@ void bn_train_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
                      scale.data_ptr<float>(), bias.data_ptr<float>(),
                      R, C, (float)momentum, (float)eps);
+  CHECK_HIP_BN(hipGetLastError());
+}
+
+// the elementwise forward pass: y = [relu](scale*x + bias [+ res])
+template <typename T>
+void bn_launch_apply(const torch::Tensor& x, torch::Tensor& y,
+                     const torch::Tensor& scale,
+                     const torch::Tensor& bias,
+                     const c10::optional<torch::Tensor>& res,
+                     torch::Tensor& mask, bool relu, long R, int C,
+                     hipStream_t stream) {
+  const long total = R * (long)C;
+  const long grid = bn_grid_elems(total / BnVec<T>::V);
+  const T* resp = res.has_value()
+      ? reinterpret_cast<const T*>(res->data_ptr()) : nullptr;
+  unsigned char* mp = mask.defined()
+      ? mask.data_ptr<unsigned char>() : nullptr;
+  #define APPLY(RELU_, RES_, WM_)                                       \
+    hipLaunchKernelGGL((bn_apply_kernel<T, RELU_, RES_, WM_>),          \
+                       dim3(grid), dim3(kT), 0, stream,                 \
+                       reinterpret_cast<const T*>(x.data_ptr()),        \
+                       reinterpret_cast<T*>(y.data_ptr()),              \
+                       scale.data_ptr<float>(), bias.data_ptr<float>(), \
+                       resp, mp, total, C)
+  const bool wm = relu && mp != nullptr;
+  if (relu && resp) { if (wm) APPLY(true, true, true);
+                      else APPLY(true, true, false); }
+  else if (relu) { if (wm) APPLY(true, false, true);
+                   else APPLY(true, false, false); }
+  else if (resp) APPLY(false, true, false);
+  else APPLY(false, false, false);
+  #undef APPLY
   CHECK_HIP_BN(hipGetLastError());
 }
 
@@ -856,42 +969,22 @@ void bn_fwd_impl(const torch::Tensor& x, torch::Tensor& y,
                        C, (float)eps);
     CHECK_HIP_BN(hipGetLastError());
   }
-  const long total = R * (long)C;
-  const long grid = bn_grid_elems(total / BnVec<T>::V);
-  const T* resp = res.has_value()
-      ? reinterpret_cast<const T*>(res->data_ptr()) : nullptr;
-  unsigned char* mp = mask.defined()
-      ? mask.data_ptr<unsigned char>() : nullptr;
-  #define APPLY(RELU_, RES_, WM_)                                       \
-    hipLaunchKernelGGL((bn_apply_kernel<T, RELU_, RES_, WM_>),          \
-                       dim3(grid), dim3(kT), 0, stream,                 \
-                       reinterpret_cast<const T*>(x.data_ptr()),        \
-                       reinterpret_cast<T*>(y.data_ptr()),              \
-                       scale.data_ptr<float>(), bias.data_ptr<float>(), \
-                       resp, mp, total, C)
-  const bool wm = relu && mp != nullptr;
-  if (relu && resp) { if (wm) APPLY(true, true, true);
-                      else APPLY(true, true, false); }
-  else if (relu) { if (wm) APPLY(true, false, true);
-                   else APPLY(true, false, false); }
-  else if (resp) APPLY(false, true, false);
-  else APPLY(false, false, false);
-  #undef APPLY
-  CHECK_HIP_BN(hipGetLastError());
+  bn_launch_apply<T>(x, y, scale, bias, res, mask, relu, R, C, stream);
 }
 
+// backward reduce -> fold: the [2, kB2, C] second-level partials of
+// sum(dy_eff) / sum(dy_eff * xhat)
 template <typename T>
-void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& mask,
-                 const torch::Tensor& x, const torch::Tensor& mean,
-                 const torch::Tensor& invstd, const torch::Tensor& gamma,
-                 torch::Tensor& dx, torch::Tensor& dgamma,
-                 torch::Tensor& dbeta,
-                 const c10::optional<torch::Tensor>& dres, bool relu,
-                 long R, int C, hipStream_t stream) {
+torch::Tensor bn_bwd_partial2(const torch::Tensor& dy,
+                              const torch::Tensor& mask,
+                              const torch::Tensor& x,
+                              const torch::Tensor& mean,
+                              const torch::Tensor& invstd, bool relu,
+                              long R, int C, hipStream_t stream) {
   const int tpr = C / BnVec<T>::V;
   const int rpb = kT / tpr;
   const int nb = bn_grid_rows(R, rpb);
-  auto fopts = gamma.options().dtype(at::kFloat);
+  auto fopts = mean.options().dtype(at::kFloat);
   auto partial = torch::empty({2, nb, C}, fopts);
   auto partial2 = torch::empty({2, kB2, C}, fopts);
   const unsigned char* mp = mask.defined()
@@ -907,24 +1000,24 @@ void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& mask,
   if (relu) RED(true); else RED(false);
   #undef RED
   CHECK_HIP_BN(hipGetLastError());
-
-  auto coefP = torch::empty({C}, fopts);
-  auto coefQ = torch::empty({C}, fopts);
-  auto coefS = torch::empty({C}, fopts);
   hipLaunchKernelGGL(bn_fold2_kernel,
                      dim3((C + kFoldC - 1) / kFoldC, kB2), dim3(kT), 0,
                      stream, partial.data_ptr<float>(), nb,
                      partial2.data_ptr<float>(), C);
   CHECK_HIP_BN(hipGetLastError());
-  hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, partial2.data_ptr<float>(),
-                     gamma.data_ptr<float>(), mean.data_ptr<float>(),
-                     invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                     dbeta.data_ptr<float>(), coefP.data_ptr<float>(),
-                     coefQ.data_ptr<float>(), coefS.data_ptr<float>(), R,
-                     C);
-  CHECK_HIP_BN(hipGetLastError());
+  return partial2;
+}
 
+// the elementwise backward pass: dx = P*dy_eff + Q*x + S [, dres]
+template <typename T>
+void bn_launch_bwd_dx(const torch::Tensor& dy, const torch::Tensor& mask,
+                      const torch::Tensor& x, const torch::Tensor& coefP,
+                      const torch::Tensor& coefQ,
+                      const torch::Tensor& coefS, torch::Tensor& dx,
+                      const c10::optional<torch::Tensor>& dres, bool relu,
+                      long R, int C, hipStream_t stream) {
+  const unsigned char* mp = mask.defined()
+      ? mask.data_ptr<unsigned char>() : nullptr;
   const long total = R * (long)C;
   const long grid = bn_grid_elems(total / BnVec<T>::V);
   T* dresp = dres.has_value()
@@ -945,6 +1038,32 @@ void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& mask,
   else DX(false, false);
   #undef DX
   CHECK_HIP_BN(hipGetLastError());
+}
+
+template <typename T>
+void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& mask,
+                 const torch::Tensor& x, const torch::Tensor& mean,
+                 const torch::Tensor& invstd, const torch::Tensor& gamma,
+                 torch::Tensor& dx, torch::Tensor& dgamma,
+                 torch::Tensor& dbeta,
+                 const c10::optional<torch::Tensor>& dres, bool relu,
+                 long R, int C, hipStream_t stream) {
+  auto fopts = gamma.options().dtype(at::kFloat);
+  torch::Tensor partial2 = bn_bwd_partial2<T>(dy, mask, x, mean, invstd,
+                                              relu, R, C, stream);
+  auto coefP = torch::empty({C}, fopts);
+  auto coefQ = torch::empty({C}, fopts);
+  auto coefS = torch::empty({C}, fopts);
+  hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256),
+                     dim3(256), 0, stream, partial2.data_ptr<float>(),
+                     gamma.data_ptr<float>(), mean.data_ptr<float>(),
+                     invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
+                     dbeta.data_ptr<float>(), coefP.data_ptr<float>(),
+                     coefQ.data_ptr<float>(), coefS.data_ptr<float>(), R,
+                     C);
+  CHECK_HIP_BN(hipGetLastError());
+  bn_launch_bwd_dx<T>(dy, mask, x, coefP, coefQ, coefS, dx, dres, relu, R,
+                      C, stream);
 }
 
 // backward fold -> coef for one BN from its [2, nb, C] partial:
@@ -1134,7 +1253,195 @@ void bn_check_input(const torch::Tensor& x, const char* what) {
               " unsupported for vec", V);
 }
 
+// The sync entry points additionally want C/V to be a power of two:
+// only then do the LDS trees of the stage-1 reductions cover every row
+// of a block.
+void bn_check_sync_input(const torch::Tensor& x, const char* what) {
+  bn_check_input(x, what);
+  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
+  const int tpr = (int)x.size(1) / V;
+  TORCH_CHECK((tpr & (tpr - 1)) == 0, what, ": C/", V,
+              " must be a power of two");
+  TORCH_CHECK(x.numel() > 0, what, ": empty input");
+}
+
+// an fp32 vector of n elements on x's device
+void bn_check_vec(const torch::Tensor& t, const torch::Tensor& x, long n,
+                  const char* what, const char* name) {
+  TORCH_CHECK(t.defined() && t.scalar_type() == at::kFloat &&
+              t.device() == x.device() && t.is_contiguous() &&
+              t.numel() == n, what, ": ", name, " must be fp32 [", n,
+              "] on the input's device");
+}
+
+void bn_check_bwd_args(const torch::Tensor& dy, const torch::Tensor& mask,
+                       const torch::Tensor& x, const torch::Tensor& mean,
+                       const torch::Tensor& invstd, bool relu,
+                       const char* what) {
+  bn_check_sync_input(x, what);
+  const int C = (int)x.size(1);
+  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
+  TORCH_CHECK(dy.sizes() == x.sizes() &&
+              dy.scalar_type() == x.scalar_type() &&
+              dy.device() == x.device(), what, ": bad gradient");
+  bn_check_vec(mean, x, C, what, "mean");
+  bn_check_vec(invstd, x, C, what, "invstd");
+  TORCH_CHECK(!relu || (mask.defined() &&
+                        mask.scalar_type() == at::kByte &&
+                        mask.device() == x.device() &&
+                        mask.numel() == x.numel() / V),
+              what, ": relu path needs the fwd mask");
+}
+
 }  // namespace
+
+// ---- synchronized BN: forward and backward cut where the sums exist.
+// No call below waits for the device or reads a value back.
+
+// Returns sums = fp32 [2C+1]: sum(x), sum(x^2) per channel, then the
+// row count N*H*W.
+torch::Tensor fused_bn_sync_stats(torch::Tensor x) {
+  bn_check_sync_input(x, "fused_bn_sync_stats");
+  const int C = (int)x.size(1);
+  const long R = x.numel() / C;
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto fopts = x.options().dtype(at::kFloat);
+  auto sums = torch::empty({2 * (long)C + 1}, fopts);
+  torch::Tensor partial2 = x.scalar_type() == at::kBFloat16
+      ? bn_stats_partial2<__hip_bfloat16>(x, fopts, R, C, stream)
+      : bn_stats_partial2<float>(x, fopts, R, C, stream);
+  hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256),
+                     dim3(256), 0, stream, partial2.data_ptr<float>(),
+                     sums.data_ptr<float>(), C, (float)R, true);
+  CHECK_HIP_BN(hipGetLastError());
+  return sums;
+}
+
+// sums: the all-reduced [2C+1]. Returns (y, mean, invstd, mask); mean
+// and invstd are the global batch statistics.
+std::vector<torch::Tensor> fused_bn_sync_apply(
+    torch::Tensor x, torch::Tensor sums, torch::Tensor gamma,
+    torch::Tensor beta, torch::Tensor running_mean,
+    torch::Tensor running_var, c10::optional<torch::Tensor> res,
+    bool relu, double momentum, double eps) {
+  const char* what = "fused_bn_sync_apply";
+  bn_check_sync_input(x, what);
+  const int C = (int)x.size(1);
+  const long R = x.numel() / C;
+  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
+  bn_check_vec(sums, x, 2 * (long)C + 1, what, "sums");
+  bn_check_vec(gamma, x, C, what, "gamma");
+  bn_check_vec(beta, x, C, what, "beta");
+  // an empty tensor stands for "no running stats", as in fused_bn_fwd
+  const bool has_running =
+      running_mean.defined() && running_mean.numel() > 0;
+  TORCH_CHECK(has_running ==
+              (running_var.defined() && running_var.numel() > 0), what,
+              ": running_mean and running_var go together");
+  if (has_running) {
+    bn_check_vec(running_mean, x, C, what, "running_mean");
+    bn_check_vec(running_var, x, C, what, "running_var");
+  }
+  if (res.has_value()) {
+    TORCH_CHECK(res->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                res->scalar_type() == x.scalar_type() &&
+                res->device() == x.device() &&
+                res->sizes() == x.sizes(), what, ": bad residual");
+  }
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto y = torch::empty_like(x);
+  auto fopts = x.options().dtype(at::kFloat);
+  auto mean = torch::empty({C}, fopts);
+  auto invstd = torch::empty({C}, fopts);
+  auto scale = torch::empty({C}, fopts);
+  auto bias = torch::empty({C}, fopts);
+  torch::Tensor mask;
+  if (relu)
+    mask = torch::empty({x.numel() / V}, x.options().dtype(at::kByte));
+  hipLaunchKernelGGL(bn_sync_stats_coef_kernel, dim3((C + 255) / 256),
+                     dim3(256), 0, stream, sums.data_ptr<float>(),
+                     gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                     has_running ? running_mean.data_ptr<float>()
+                                 : nullptr,
+                     has_running ? running_var.data_ptr<float>()
+                                 : nullptr,
+                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                     scale.data_ptr<float>(), bias.data_ptr<float>(), C,
+                     (float)momentum, (float)eps);
+  CHECK_HIP_BN(hipGetLastError());
+  if (x.scalar_type() == at::kBFloat16)
+    bn_launch_apply<__hip_bfloat16>(x, y, scale, bias, res, mask, relu, R,
+                                    C, stream);
+  else
+    bn_launch_apply<float>(x, y, scale, bias, res, mask, relu, R, C,
+                           stream);
+  if (!mask.defined())
+    mask = torch::empty({0}, x.options().dtype(at::kByte));
+  return {y, mean, invstd, mask};
+}
+
+// Returns bsums = fp32 [2C]: sum(dy_eff) (this rank's dbeta), then
+// sum(dy_eff * xhat) (its dgamma).
+torch::Tensor fused_bn_sync_bwd_reduce(
+    torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
+    torch::Tensor mean, torch::Tensor invstd, bool relu) {
+  bn_check_bwd_args(dy, mask, x, mean, invstd, relu,
+                    "fused_bn_sync_bwd_reduce");
+  const int C = (int)x.size(1);
+  const long R = x.numel() / C;
+  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto bsums = torch::empty({2 * (long)C}, mean.options());
+  torch::Tensor partial2 = x.scalar_type() == at::kBFloat16
+      ? bn_bwd_partial2<__hip_bfloat16>(dy, mask, x, mean, invstd, relu,
+                                        R, C, stream)
+      : bn_bwd_partial2<float>(dy, mask, x, mean, invstd, relu, R, C,
+                               stream);
+  hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256),
+                     dim3(256), 0, stream, partial2.data_ptr<float>(),
+                     bsums.data_ptr<float>(), C, 0.f, false);
+  CHECK_HIP_BN(hipGetLastError());
+  return bsums;
+}
+
+// bsums: the all-reduced [2C]; count: the 1-element global row count
+// (the last word of the forward's reduced sums). Returns (dx[, dres]).
+std::vector<torch::Tensor> fused_bn_sync_bwd_dx(
+    torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
+    torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma,
+    torch::Tensor bsums, torch::Tensor count, bool relu, bool has_res) {
+  const char* what = "fused_bn_sync_bwd_dx";
+  bn_check_bwd_args(dy, mask, x, mean, invstd, relu, what);
+  const int C = (int)x.size(1);
+  const long R = x.numel() / C;
+  bn_check_vec(gamma, x, C, what, "gamma");
+  bn_check_vec(bsums, x, 2 * (long)C, what, "bsums");
+  bn_check_vec(count, x, 1, what, "count");
+  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto dx = torch::empty_like(x);
+  auto coefP = torch::empty({C}, mean.options());
+  auto coefQ = torch::empty({C}, mean.options());
+  auto coefS = torch::empty({C}, mean.options());
+  c10::optional<torch::Tensor> dres;
+  if (has_res) dres = torch::empty_like(x);
+  hipLaunchKernelGGL(bn_sync_bwd_coef_kernel, dim3((C + 255) / 256),
+                     dim3(256), 0, stream, bsums.data_ptr<float>(),
+                     count.data_ptr<float>(), gamma.data_ptr<float>(),
+                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                     coefP.data_ptr<float>(), coefQ.data_ptr<float>(),
+                     coefS.data_ptr<float>(), C);
+  CHECK_HIP_BN(hipGetLastError());
+  if (x.scalar_type() == at::kBFloat16)
+    bn_launch_bwd_dx<__hip_bfloat16>(dy, mask, x, coefP, coefQ, coefS, dx,
+                                     dres, relu, R, C, stream);
+  else
+    bn_launch_bwd_dx<float>(dy, mask, x, coefP, coefQ, coefS, dx, dres,
+                            relu, R, C, stream);
+  std::vector<torch::Tensor> out = {dx};
+  if (has_res) out.push_back(*dres);
+  return out;
+}
 
 // BN(train) + ReLU + MaxPool2d(3, stride 2, pad 1).
 // Returns (pooled, save_mean, save_invstd, code); code holds one 32-bit

@@ -995,6 +995,21 @@ std::vector<torch::Tensor> fused_bn_dual_bwd(
     torch::Tensor xd, torch::Tensor mean3, torch::Tensor invstd3,
     torch::Tensor gamma3, torch::Tensor meand, torch::Tensor invstdd,
     torch::Tensor gammad);
+// synchronized BN: fused_bn_fwd / fused_bn_bwd cut where the per-channel
+// sums exist, for an all-reduce in between — defined in fused_bn.hip
+torch::Tensor fused_bn_sync_stats(torch::Tensor x);
+std::vector<torch::Tensor> fused_bn_sync_apply(
+    torch::Tensor x, torch::Tensor sums, torch::Tensor gamma,
+    torch::Tensor beta, torch::Tensor running_mean,
+    torch::Tensor running_var, c10::optional<torch::Tensor> res,
+    bool relu, double momentum, double eps);
+torch::Tensor fused_bn_sync_bwd_reduce(
+    torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
+    torch::Tensor mean, torch::Tensor invstd, bool relu);
+std::vector<torch::Tensor> fused_bn_sync_bwd_dx(
+    torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
+    torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma,
+    torch::Tensor bsums, torch::Tensor count, bool relu, bool has_res);
 
 // flash attention (causal, hs=64) — defined in flash_attn.hip
 std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
@@ -1180,6 +1195,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused NHWC relu(BN(x3) + BN(xd)) forward");
   m.def("fused_bn_dual_bwd", &fused_bn_dual_bwd,
         "fused NHWC relu(BN(x3) + BN(xd)) backward");
+  m.def("fused_bn_sync_stats", &fused_bn_sync_stats,
+        "sync BN: local per-channel sum / sumsq and row count [2C+1]");
+  m.def("fused_bn_sync_apply", &fused_bn_sync_apply,
+        "sync BN: coefficients from reduced sums, then the apply pass");
+  m.def("fused_bn_sync_bwd_reduce", &fused_bn_sync_bwd_reduce,
+        "sync BN: local sum(dy) / sum(dy*xhat) [2C]");
+  m.def("fused_bn_sync_bwd_dx", &fused_bn_sync_bwd_dx,
+        "sync BN: dx coefficients from reduced sums, then the dx pass");
   m.def("fused_ln_fwd", &fused_ln_fwd,
         "fused (dropout +) residual-add + LayerNorm forward");
   m.def("fused_ln_bwd", &fused_ln_bwd,

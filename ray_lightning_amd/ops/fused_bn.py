@@ -11,6 +11,10 @@ Drop-in: ``FusedBatchNorm2d`` subclasses ``nn.BatchNorm2d`` (same
 parameters/buffers/state_dict). The fused HIP path engages on GPU for
 channels_last bf16/fp32 inputs; anything else falls back to composed
 torch ops so CPU tests and odd shapes stay correct.
+
+``FusedSyncBatchNorm2d`` / ``convert_sync_batchnorm`` (end of this file)
+take the training-mode statistics over all ranks of a communicator, on
+the same kernels cut where the per-channel sums exist.
 """
 from __future__ import annotations
 
@@ -193,12 +197,19 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
             out = torch.relu(out)
         return out
 
+    def _sync_active(self) -> bool:
+        """True when this forward reduces its statistics across ranks
+        (``FusedSyncBatchNorm2d`` in training mode with more than one
+        rank). The stem and junction fusions then stay composed."""
+        return False
+
     def forward_pool(self, x: torch.Tensor,
                      pool: nn.Module) -> torch.Tensor:
         """``pool(self(x))``; one fused BN+ReLU+maxpool kernel set when
         training with ReLU and ``pool`` is MaxPool2d(3, stride 2,
         padding 1)."""
         if self.training and self.relu and _pool_is_3_2_1(pool) and \
+                not self._sync_active() and \
                 self._kernel_ready(x) and x.numel() < 2 ** 31:
             return _FusedBNReluPoolFunction.apply(
                 x, self.weight, self.bias, self.running_mean,
@@ -213,6 +224,8 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
         if self.training and self.relu and \
                 isinstance(other_bn, FusedBatchNorm2d) and \
                 other_bn.training and not other_bn.relu and \
+                not self._sync_active() and \
+                not other_bn._sync_active() and \
                 other_x.shape == x.shape and other_x.dtype == x.dtype and \
                 self._kernel_ready(x) and other_bn._kernel_ready(other_x):
             momentumd = other_bn._step_momentum()
@@ -222,3 +235,258 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
                 other_bn.running_mean, other_bn.running_var,
                 self._step_momentum(), momentumd, self.eps, other_bn.eps)
         return self(x, other_bn(other_x))
+
+
+# ---------------------------------------------------------------------
+# synchronized BN: batch statistics over all ranks
+#
+# The forward and the backward are each cut where the per-channel sums
+# exist; the sums are all-reduced there and the coefficients derived
+# from the global sums and the global row count. Each of the four
+# phases has a HIP backend (the extension's fused_bn_sync_* entry
+# points) and a torch twin that forms the same fp32 sums, so CPU runs go
+# through the same communication choreography.
+#   sums  = [sum(x) | sum(x^2) | row count]     fp32 [2C+1]
+#   bsums = [sum(dy_eff) | sum(dy_eff * xhat)]  fp32 [2C]
+# ---------------------------------------------------------------------
+def _sync_kernel_shape(x: torch.Tensor, c: int) -> bool:
+    """The sync entry points additionally want C/V to be a power of two:
+    only then do the stage-1 reduction trees cover every row of a
+    block."""
+    tpr = c // (8 if x.dtype == torch.bfloat16 else 4)
+    return tpr > 0 and tpr & (tpr - 1) == 0
+
+
+def _per_channel(v: torch.Tensor) -> torch.Tensor:
+    return v.view(1, -1, 1, 1)
+
+
+def _twin_stats(x: torch.Tensor) -> torch.Tensor:
+    c = x.shape[1]
+    xw = x.to(torch.promote_types(x.dtype, torch.float32))
+    count = xw.new_full((1,), x.numel() // c)
+    return torch.cat([xw.sum(dim=(0, 2, 3)), (xw * xw).sum(dim=(0, 2, 3)),
+                      count]).float()
+
+
+def _twin_apply(x, sums, weight, bias, running_mean, running_var, res,
+                relu, momentum, eps):
+    c = x.shape[1]
+    count = sums[2 * c]
+    mean = sums[:c] / count
+    var = (sums[c:2 * c] / count - mean * mean).clamp_min(0.0)
+    invstd = torch.rsqrt(var + eps)
+    if running_mean is not None:
+        var_unb = torch.where(count > 1, var * count / (count - 1), var)
+        running_mean.mul_(1.0 - momentum).add_(
+            mean.to(running_mean.dtype), alpha=momentum)
+        running_var.mul_(1.0 - momentum).add_(
+            var_unb.to(running_var.dtype), alpha=momentum)
+    scale = invstd if weight is None else weight.float() * invstd
+    shift = -mean * scale
+    if bias is not None:
+        shift = shift + bias.float()
+    out_dtype = x.dtype if res is None else \
+        torch.result_type(x, res)
+    y = x.float() * _per_channel(scale) + _per_channel(shift)
+    if res is not None:
+        y = y + res.float()
+    mask = None
+    if relu:
+        mask = y > 0
+        y = torch.relu(y)
+    return y.to(out_dtype), mean, invstd, mask
+
+
+def _twin_dy_eff(dy, mask, relu):
+    d = dy.float()
+    return d * mask if relu else d
+
+
+def _twin_bwd_reduce(dy, mask, x, mean, invstd, relu):
+    d = _twin_dy_eff(dy, mask, relu)
+    xhat = (x.float() - _per_channel(mean)) * _per_channel(invstd)
+    return torch.cat([d.sum(dim=(0, 2, 3)), (d * xhat).sum(dim=(0, 2, 3))])
+
+
+def _twin_bwd_dx(dy, mask, x, mean, invstd, weight, bsums, count, relu):
+    """dx = P*dy_eff + Q*x + S with the coefficients of
+    bn_bwd_coef_kernel; also returns dy_eff (the residual's gradient)."""
+    c = x.shape[1]
+    d = _twin_dy_eff(dy, mask, relu)
+    p = invstd if weight is None else weight.float() * invstd
+    q = -p * invstd * bsums[c:] / count
+    s = -p * bsums[:c] / count - q * mean
+    dx = _per_channel(p) * d + _per_channel(q) * x.float() + \
+        _per_channel(s)
+    return dx.to(x.dtype), d
+
+
+class _FusedSyncBNFunction(torch.autograd.Function):
+    """Training-mode BN(+ReLU)(+residual) with statistics over all ranks
+    of ``comm``. One all-reduce in forward, one in backward, both
+    synchronous on the caller's stream."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean,
+                running_var, momentum, eps, relu, comm, use_ext):
+        c = x.shape[1]
+        if use_ext:
+            ext = _load_ext()
+            sums = ext.fused_bn_sync_stats(x)
+        else:
+            sums = _twin_stats(x)
+        comm.all_reduce_(sums, op="sum", async_op=False)
+        if use_ext:
+            y, mean, invstd, mask = ext.fused_bn_sync_apply(
+                x, sums, weight, bias,
+                running_mean if running_mean is not None
+                else torch.Tensor(),
+                running_var if running_var is not None
+                else torch.Tensor(),
+                residual, relu, momentum, eps)
+        else:
+            y, mean, invstd, mask = _twin_apply(
+                x, sums, weight, bias, running_mean, running_var,
+                residual, relu, momentum, eps)
+        ctx.relu = relu
+        ctx.use_ext = use_ext
+        ctx.comm = comm
+        ctx.res_dtype = None if residual is None else residual.dtype
+        # the global row count stays on the device for backward
+        ctx.save_for_backward(x, mask, mean, invstd, weight,
+                              sums[2 * c:])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mask, mean, invstd, weight, count = ctx.saved_tensors
+        c = x.shape[1]
+        has_res = ctx.res_dtype is not None
+        if ctx.use_ext:
+            ext = _load_ext()
+            bsums = ext.fused_bn_sync_bwd_reduce(dy, mask, x, mean,
+                                                 invstd, ctx.relu)
+        else:
+            bsums = _twin_bwd_reduce(dy, mask, x, mean, invstd, ctx.relu)
+        # dgamma/dbeta stay this rank's sums (torch.nn.SyncBatchNorm
+        # semantics): the gradient engine averages them like any other
+        # gradient
+        local = bsums.clone()
+        ctx.comm.all_reduce_(bsums, op="sum", async_op=False)
+        if ctx.use_ext:
+            outs = ext.fused_bn_sync_bwd_dx(
+                dy, mask, x, mean, invstd, weight, bsums, count,
+                ctx.relu, has_res)
+            dx = outs[0]
+            dres = outs[1] if has_res else None
+        else:
+            dx, d = _twin_bwd_dx(dy, mask, x, mean, invstd, weight,
+                                 bsums, count, ctx.relu)
+            dres = d.to(ctx.res_dtype) if has_res else None
+        dgamma = dbeta = None
+        if weight is not None:
+            dbeta = local[:c].to(weight.dtype)
+            dgamma = local[c:].to(weight.dtype)
+        return (dx, dres, dgamma, dbeta, None, None, None, None, None,
+                None, None)
+
+
+class FusedSyncBatchNorm2d(FusedBatchNorm2d):
+    """``FusedBatchNorm2d`` whose training-mode statistics span all ranks
+    of ``comm`` (an ``engine.comm.Communicator``).
+
+    Same parameters, buffers and ``state_dict`` keys; ``comm`` is not
+    state and is dropped on pickling and copying. In eval mode, with
+    ``comm is None`` or with one rank, this is ``FusedBatchNorm2d``
+    exactly. Otherwise every training-mode forward, also under
+    ``torch.no_grad()`` or ``NativeDDP.no_sync()``, all-reduces the
+    per-channel sums and the row count, so ranks may hold different
+    batch sizes but must run the same number of training forwards.
+    ``forward_pool`` and ``forward_dual`` then take their composed
+    forms and synchronise through ``forward``."""
+
+    def __init__(self, num_features: int, relu: bool = False, comm=None,
+                 **kwargs):
+        super().__init__(num_features, relu=relu, **kwargs)
+        self.comm = comm
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["comm"] = None  # live process-group handles do not travel
+        return state
+
+    def _sync_active(self) -> bool:
+        return self.training and self.comm is not None and \
+            self.comm.world_size > 1
+
+    def forward(self, x: torch.Tensor,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not self._sync_active():
+            return super().forward(x, residual)
+        self._check_input_dim(x)
+        use_ext = self._kernel_ready(x) and \
+            _sync_kernel_shape(x, self.num_features) and \
+            self.bias is not None and \
+            (residual is None or (residual.dtype == x.dtype and
+                                  residual.shape == x.shape)) and \
+            (self.running_mean is None or
+             self.running_mean.dtype == torch.float32)
+        if use_ext and residual is not None:
+            residual = residual.contiguous(
+                memory_format=torch.channels_last)
+        return _FusedSyncBNFunction.apply(
+            x, residual, self.weight, self.bias, self.running_mean,
+            self.running_var, self._step_momentum(), self.eps, self.relu,
+            self.comm, use_ext)
+
+
+def convert_sync_batchnorm(module: nn.Module, comm) -> nn.Module:
+    """Replace every ``nn.BatchNorm2d`` in ``module`` (``FusedBatchNorm2d``
+    included, keeping its ``relu`` flag) with a ``FusedSyncBatchNorm2d``
+    bound to ``comm``. The replacement carries the same Parameter and
+    buffer objects, so optimizers built earlier stay valid. A module
+    that already is a ``FusedSyncBatchNorm2d`` is kept and rebound to
+    ``comm``. ``BatchNorm1d``/``BatchNorm3d`` are left alone, with one
+    warning that names them. Returns the converted module (a new object
+    only when ``module`` itself is a BatchNorm2d)."""
+    skipped: list = []
+    out = _convert_sync(module, comm, "", {}, skipped)
+    if skipped:
+        import warnings
+        warnings.warn(
+            "convert_sync_batchnorm only synchronises BatchNorm2d; left "
+            "with per-rank statistics: " + ", ".join(skipped))
+    return out
+
+
+def _convert_sync(module, comm, name, memo, skipped):
+    if id(module) in memo:
+        return memo[id(module)]
+    out = module
+    if isinstance(module, FusedSyncBatchNorm2d):
+        module.comm = comm
+    elif isinstance(module, nn.BatchNorm2d):
+        out = FusedSyncBatchNorm2d(
+            module.num_features, relu=getattr(module, "relu", False),
+            comm=comm, eps=module.eps, momentum=module.momentum,
+            affine=module.affine,
+            track_running_stats=module.track_running_stats)
+        if module.affine:
+            out.weight = module.weight
+            out.bias = module.bias
+        if module.track_running_stats:
+            out.running_mean = module.running_mean
+            out.running_var = module.running_var
+            out.num_batches_tracked = module.num_batches_tracked
+        out.training = module.training
+    elif isinstance(module, (nn.BatchNorm1d, nn.BatchNorm3d)):
+        skipped.append(f"{name or '<root>'} ({type(module).__name__})")
+    memo[id(module)] = out
+    for child_name, child in module.named_children():
+        new = _convert_sync(child, comm,
+                            f"{name}.{child_name}" if name else child_name,
+                            memo, skipped)
+        if new is not child:
+            module.add_module(child_name, new)
+    return out

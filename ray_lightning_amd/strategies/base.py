@@ -81,6 +81,13 @@ class Strategy:
         them)."""
 
     # -- collectives ----------------------------------------------------------
+    def data_communicator(self):
+        """The communicator the gradient engine reduces on, or None when
+        there is a single process. ``Trainer(sync_batchnorm=True)`` binds
+        the BN layers to it, so that every collective of a rank is issued
+        on one communicator, in one order."""
+        return None
+
     def reduce(self, tensor: torch.Tensor, op: str = "mean") -> torch.Tensor:
         return tensor
 

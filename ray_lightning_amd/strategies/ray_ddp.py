@@ -257,6 +257,9 @@ class RayStrategy(Strategy):
             return model
         return NativeDDP(model, self._data_comm, **self._ddp_kwargs)
 
+    def data_communicator(self) -> Optional[Communicator]:
+        return self._data_comm
+
     def reduce(self, tensor: torch.Tensor, op: str = "mean"):
         if self._comm is None:
             return tensor

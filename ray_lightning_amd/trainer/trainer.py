@@ -76,6 +76,7 @@ class Trainer:
                  enable_model_summary: bool = False,
                  reload_dataloaders_every_n_epochs: int = 0,
                  resume_from_checkpoint: Optional[str] = None,
+                 sync_batchnorm: bool = False,
                  **_ignored):
         if isinstance(strategy, str):
             from ..strategies import STRATEGY_REGISTRY
@@ -110,6 +111,8 @@ class Trainer:
                 "gradient_clip_algorithm must be 'norm' or 'value', got "
                 f"{gradient_clip_algorithm!r}")
         self.gradient_clip_algorithm = gradient_clip_algorithm
+        # BatchNorm2d statistics over all ranks (no effect on one rank)
+        self.sync_batchnorm = bool(sync_batchnorm)
         # global grad norm of the last clip; a tensor the trainer never
         # synchronises (None until the first clipped step)
         self.last_grad_norm: Optional[torch.Tensor] = None
@@ -337,6 +340,16 @@ class Trainer:
         model.setup(stage_name)
         for cb in self.callbacks:
             cb.setup(self, model, stage_name)
+
+        # sync BN: swap the BatchNorm2d layers before the optimizer is
+        # built (the parameters stay the same objects). Every stage
+        # converts, so a model always carries this stage's communicator;
+        # eval-mode BN never communicates.
+        if self.sync_batchnorm and self.strategy.world_size > 1:
+            comm = self.strategy.data_communicator()
+            if comm is not None:
+                from ..ops.fused_bn import convert_sync_batchnorm
+                convert_sync_batchnorm(model, comm)
 
         model.to(device)
 
