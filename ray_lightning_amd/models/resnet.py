@@ -15,6 +15,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
+from ..ops.conv1x1 import WIRED_WIDTHS, conv1x1_bwd_enabled, conv1x1_fork
 from ..ops.fused_bn import FusedBatchNorm2d, bn_fusions_enabled
 
 
@@ -42,9 +43,19 @@ class Bottleneck(nn.Module):
             isinstance(downsample[0], nn.Conv2d) and \
             isinstance(downsample[1], FusedBatchNorm2d)
 
+        # conv1's input gradient and the skip gradient leave one kernel
+        # (RLA_CONV1X1_BWD, read once here) at the widths it is wired for
+        self._conv1_fork = conv1x1_bwd_enabled() and width in WIRED_WIDTHS
+
     def forward(self, x):
+        if self._conv1_fork:
+            # x from here on is the alias whose gradient meets conv1's
+            # in conv1x1_fork's backward
+            out, x = conv1x1_fork(x, self.conv1.weight, True)
+            out = self.bn1(out)
+        else:
+            out = self.bn1(self.conv1(x))
         identity = x
-        out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
         if self._dual_bn:
             return self.bn3.forward_dual(self.conv3(out),

@@ -1054,6 +1054,12 @@ std::vector<torch::Tensor> flash_attn_fwd_v4(torch::Tensor q,
                                              torch::Tensor k,
                                              torch::Tensor v,
                                              double scale);
+// 1x1 stride-1 conv input gradient (+ skip gradient) — defined in
+// conv1x1_bwd.hip
+torch::Tensor conv1x1_bwd_data(torch::Tensor dy, torch::Tensor w,
+                               c10::optional<torch::Tensor> skip);
+bool conv1x1_bwd_data_supported(long cout, long cin);
+long conv1x1_bwd_data_row_tile(long cout, long cin);
 // layout / instruction-semantics probes — defined in mfma_probe.hip
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor permlane_swap_probe();
@@ -1223,6 +1229,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "v3 flash attention fwd with document masking and dropout");
   m.def("flash_attn_bwd_v3_docs_dropout", &flash_attn_bwd_v3_docs_dropout,
         "v3 flash attention bwd with document masking and dropout");
+  m.def("conv1x1_bwd_data", &conv1x1_bwd_data,
+        "dx = dy . w (+ skip) for a 1x1 stride-1 NHWC bf16 convolution",
+        pybind11::arg("dy"), pybind11::arg("w"),
+        pybind11::arg("skip") = pybind11::none());
+  m.def("conv1x1_bwd_data_supported", &conv1x1_bwd_data_supported,
+        "whether conv1x1_bwd_data has a kernel for (Cout, Cin)");
+  m.def("conv1x1_bwd_data_row_tile", &conv1x1_bwd_data_row_tile,
+        "rows per workgroup tile of conv1x1_bwd_data for (Cout, Cin)");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");
