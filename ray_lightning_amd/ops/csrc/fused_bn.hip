@@ -72,6 +72,44 @@ __device__ __forceinline__ void load_coef(float (&dst)[V],
         *reinterpret_cast<const float4*>(src + i);
 }
 
+// How the kT threads of a stage-1 block cover rows of [R, C]: tpr = C/V
+// threads share a row, each with V channels from c0; a block holds
+// rpb = kT/tpr rows. The host check admits only a power-of-two
+// tpr <= kT, so tpr * rpb == kT and the tree of bn_block_fold, which
+// halves rpb, reaches every row of the block.
+template <int V>
+struct BnRowMap {
+  int tpr, rpb, slot, row_in_block, c0;
+  __device__ __forceinline__ explicit BnRowMap(int C)
+      : tpr(C / V), rpb(kT / tpr), slot(threadIdx.x % tpr),
+        row_in_block(threadIdx.x / tpr), c0(slot * V) {}
+};
+
+// fold one per-thread accumulator across the rpb rows of a block that
+// share a channel slot and store the block's row of a partial plane
+template <int V>
+__device__ __forceinline__ void bn_block_fold(
+    float* __restrict__ lds, const float (&a)[V],
+    float* __restrict__ plane_row, const BnRowMap<V>& map) {
+  #pragma unroll
+  for (int i = 0; i < V; ++i) lds[threadIdx.x * V + i] = a[i];
+  __syncthreads();
+  for (int s = map.rpb / 2; s > 0; s >>= 1) {
+    if (map.row_in_block < s) {
+      #pragma unroll
+      for (int i = 0; i < V; ++i)
+        lds[threadIdx.x * V + i] +=
+            lds[(threadIdx.x + s * map.tpr) * V + i];
+    }
+    __syncthreads();
+  }
+  if (map.row_in_block == 0) {
+    #pragma unroll
+    for (int i = 0; i < V; ++i) plane_row[i] = lds[threadIdx.x * V + i];
+  }
+  __syncthreads();
+}
+
 // --------------------------------------------------------------------
 // stage 1 stats: per-(block, channel) partial sum / sumsq
 // partial layout: [2, nblocks, C] (sum plane then sumsq plane)
@@ -81,21 +119,17 @@ __global__ __launch_bounds__(kT) void bn_stats_kernel(
     const T* __restrict__ x, float* __restrict__ partial, long R,
     int C) {
   constexpr int V = BnVec<T>::V;
-  const int tpr = C / V;             // threads per row (<= kT)
-  const int rpb = kT / tpr;          // rows per block (power of 2)
-  const int slot = threadIdx.x % tpr;
-  const int row_in_block = threadIdx.x / tpr;
-  const int c0 = slot * V;
+  const BnRowMap<V> map(C);
 
   float acc[V], acc2[V];
   #pragma unroll
   for (int i = 0; i < V; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
 
-  const long row_stride = (long)gridDim.x * rpb;
-  for (long r = (long)blockIdx.x * rpb + row_in_block; r < R;
+  const long row_stride = (long)gridDim.x * map.rpb;
+  for (long r = (long)blockIdx.x * map.rpb + map.row_in_block; r < R;
        r += row_stride) {
     T v[V];
-    load_vec<T, V>(v, x + r * C + c0);
+    load_vec<T, V>(v, x + r * C + map.c0);
     #pragma unroll
     for (int i = 0; i < V; ++i) {
       const float f = bn_tof<T>(v[i]);
@@ -106,29 +140,9 @@ __global__ __launch_bounds__(kT) void bn_stats_kernel(
 
   __shared__ float lds[kT * BnVec<T>::V];
   const long nbC = (long)gridDim.x * C;
-  // reduce sum then sumsq across the rpb rows sharing a channel slot
-  for (int pass = 0; pass < 2; ++pass) {
-    #pragma unroll
-    for (int i = 0; i < V; ++i)
-      lds[threadIdx.x * V + i] = pass ? acc2[i] : acc[i];
-    __syncthreads();
-    for (int s = rpb / 2; s > 0; s >>= 1) {
-      if (row_in_block < s) {
-        #pragma unroll
-        for (int i = 0; i < V; ++i)
-          lds[threadIdx.x * V + i] +=
-              lds[(threadIdx.x + s * tpr) * V + i];
-      }
-      __syncthreads();
-    }
-    if (row_in_block == 0) {
-      #pragma unroll
-      for (int i = 0; i < V; ++i)
-        partial[pass * nbC + (long)blockIdx.x * C + c0 + i] =
-            lds[threadIdx.x * V + i];
-    }
-    __syncthreads();
-  }
+  float* row = partial + (long)blockIdx.x * C + map.c0;
+  bn_block_fold<V>(lds, acc, row, map);
+  bn_block_fold<V>(lds, acc2, row + nbC, map);
 }
 
 // --------------------------------------------------------------------
@@ -177,60 +191,84 @@ __global__ __launch_bounds__(kT) void bn_fold2_kernel(
   partial2[b2C + (long)blockIdx.y * C + c] = lsq[threadIdx.x];
 }
 
-__global__ void bn_stats_coef_kernel(
-    const float* __restrict__ partial2,
-    const float* __restrict__ gamma, const float* __restrict__ beta,
-    float* __restrict__ running_mean, float* __restrict__ running_var,
-    float* __restrict__ mean_out, float* __restrict__ invstd_out,
-    float* __restrict__ scale_out, float* __restrict__ bias_out,
-    long R, int C, float momentum, float eps) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
+// the two planes of a [2, kB2, C] second-level partial, folded for
+// channel c
+__device__ __forceinline__ void bn_fold_b2(
+    const float* __restrict__ partial2, int C, int c, float& s,
+    float& s2) {
   const long b2C = (long)kB2 * C;
-  float s = 0.f, s2 = 0.f;
+  s = 0.f;
+  s2 = 0.f;
   #pragma unroll
   for (int b = 0; b < kB2; ++b) {
     s += partial2[(long)b * C + c];
     s2 += partial2[b2C + (long)b * C + c];
   }
-  const float m = s / (float)R;
-  const float var = fmaxf(s2 / (float)R - m * m, 0.f);
-  const float inv = rsqrtf(var + eps);
-  mean_out[c] = m;
-  invstd_out[c] = inv;
-  const float sc = gamma[c] * inv;
-  scale_out[c] = sc;
-  bias_out[c] = beta[c] - m * sc;
-  if (running_mean != nullptr) {
+}
+
+// per-channel operands and results of the forward coefficient kernels
+struct BnFwdCoef {
+  const float* gamma;
+  const float* beta;
+  float* running_mean;  // null: no running stats
+  float* running_var;
+  float* mean;
+  float* invstd;
+  float* scale;
+  float* bias;
+  float momentum, eps;
+};
+
+// mean/invstd, the apply pass's scale/bias and the running-stat update
+// of channel c from its sums. Rf is the row count and Rm1 the row count
+// less one, each converted to fp32 by the caller in its own way.
+__device__ __forceinline__ void bn_fwd_coefs(const BnFwdCoef& a, int c,
+                                             float s, float s2, float Rf,
+                                             float Rm1) {
+  const float m = s / Rf;
+  const float var = fmaxf(s2 / Rf - m * m, 0.f);
+  const float inv = rsqrtf(var + a.eps);
+  a.mean[c] = m;
+  a.invstd[c] = inv;
+  const float sc = a.gamma[c] * inv;
+  a.scale[c] = sc;
+  a.bias[c] = a.beta[c] - m * sc;
+  if (a.running_mean != nullptr) {
     // unbiased variance for running stats (torch semantics)
-    const float var_unb = R > 1 ? var * (float)R / (float)(R - 1) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    running_var[c] = (1.f - momentum) * running_var[c] +
-                     momentum * var_unb;
+    const float var_unb = Rf > 1.f ? var * Rf / Rm1 : var;
+    a.running_mean[c] =
+        (1.f - a.momentum) * a.running_mean[c] + a.momentum * m;
+    a.running_var[c] =
+        (1.f - a.momentum) * a.running_var[c] + a.momentum * var_unb;
   }
 }
 
+__global__ void bn_stats_coef_kernel(
+    const float* __restrict__ partial2, BnFwdCoef a, long R, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float s, s2;
+  bn_fold_b2(partial2, C, c, s, s2);
+  bn_fwd_coefs(a, c, s, s2, (float)R, (float)(R - 1));
+}
+
 // --------------------------------------------------------------------
-// synchronized BN: the forward and backward above, cut where the
-// per-channel sums exist so that they can be all-reduced across ranks.
+// synchronized BN: the forward and backward, cut where the per-channel
+// sums exist so that they can be all-reduced across ranks.
 // sums = [2C+1]: sum(x), sum(x^2), then the row count as one fp32 word
 // (summed over ranks it is off by at most 2^-24 relative, below the
 // rounding of the sums themselves). bsums = [2C]: sum(dy_eff),
-// sum(dy_eff * xhat). The kB2 rows are folded in the order of
-// bn_stats_coef_kernel / bn_bwd_coef_kernel: one rank gives their bits.
+// sum(dy_eff * xhat). The kB2 rows are folded and the coefficients
+// formed by the device functions of the plain kernels: one rank gives
+// their bits.
 // --------------------------------------------------------------------
 __global__ void bn_sync_fold_kernel(
     const float* __restrict__ partial2, float* __restrict__ sums, int C,
     float count, bool with_count) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const long b2C = (long)kB2 * C;
-  float s = 0.f, s2 = 0.f;
-  #pragma unroll
-  for (int b = 0; b < kB2; ++b) {
-    s += partial2[(long)b * C + c];
-    s2 += partial2[b2C + (long)b * C + c];
-  }
+  float s, s2;
+  bn_fold_b2(partial2, C, c, s, s2);
   sums[c] = s;
   sums[C + c] = s2;
   if (with_count && c == 0) sums[2 * C] = count;
@@ -239,47 +277,11 @@ __global__ void bn_sync_fold_kernel(
 // bn_stats_coef_kernel on reduced sums, the global row count read from
 // the device
 __global__ void bn_sync_stats_coef_kernel(
-    const float* __restrict__ sums, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float* __restrict__ running_mean,
-    float* __restrict__ running_var, float* __restrict__ mean_out,
-    float* __restrict__ invstd_out, float* __restrict__ scale_out,
-    float* __restrict__ bias_out, int C, float momentum, float eps) {
+    const float* __restrict__ sums, BnFwdCoef a, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float R = sums[2 * C];
-  const float m = sums[c] / R;
-  const float var = fmaxf(sums[C + c] / R - m * m, 0.f);
-  const float inv = rsqrtf(var + eps);
-  mean_out[c] = m;
-  invstd_out[c] = inv;
-  const float sc = gamma[c] * inv;
-  scale_out[c] = sc;
-  bias_out[c] = beta[c] - m * sc;
-  if (running_mean != nullptr) {
-    const float var_unb = R > 1.f ? var * R / (R - 1.f) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    running_var[c] = (1.f - momentum) * running_var[c] +
-                     momentum * var_unb;
-  }
-}
-
-// bn_bwd_coef_kernel on reduced sums; dgamma/dbeta stay the caller's
-// local sums
-__global__ void bn_sync_bwd_coef_kernel(
-    const float* __restrict__ bsums, const float* __restrict__ count,
-    const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float* __restrict__ coefP,
-    float* __restrict__ coefQ, float* __restrict__ coefS, int C) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float dsum = bsums[c];
-  const float dxhat = bsums[C + c];
-  const float invR = 1.f / count[0];
-  const float P = gamma[c] * invstd[c];
-  const float Q = -P * invstd[c] * dxhat * invR;
-  coefP[c] = P;
-  coefQ[c] = Q;
-  coefS[c] = -P * dsum * invR - Q * mean[c];
+  bn_fwd_coefs(a, c, sums[c], sums[C + c], R, R - 1.f);
 }
 
 // eval mode: scale/bias straight from running stats
@@ -349,28 +351,24 @@ __global__ __launch_bounds__(kT) void bn_bwd_reduce_kernel(
     const float* __restrict__ invstd, float* __restrict__ partial,
     long R, int C) {
   constexpr int V = BnVec<T>::V;
-  const int tpr = C / V;
-  const int rpb = kT / tpr;
-  const int slot = threadIdx.x % tpr;
-  const int row_in_block = threadIdx.x / tpr;
-  const int c0 = slot * V;
+  const BnRowMap<V> map(C);
 
   float mu[V], is[V];
-  load_coef<V>(mu, mean + c0);
-  load_coef<V>(is, invstd + c0);
+  load_coef<V>(mu, mean + map.c0);
+  load_coef<V>(is, invstd + map.c0);
 
   float a0[V], a1[V];
   #pragma unroll
   for (int i = 0; i < V; ++i) { a0[i] = 0.f; a1[i] = 0.f; }
 
-  const long row_stride = (long)gridDim.x * rpb;
-  for (long r = (long)blockIdx.x * rpb + row_in_block; r < R;
+  const long row_stride = (long)gridDim.x * map.rpb;
+  for (long r = (long)blockIdx.x * map.rpb + map.row_in_block; r < R;
        r += row_stride) {
     T dv[V], xv[V];
-    load_vec<T, V>(dv, dy + r * C + c0);
-    load_vec<T, V>(xv, x + r * C + c0);
+    load_vec<T, V>(dv, dy + r * C + map.c0);
+    load_vec<T, V>(xv, x + r * C + map.c0);
     unsigned int m = 0xffu;
-    if constexpr (RELU) m = mask[(r * C + c0) / V];
+    if constexpr (RELU) m = mask[(r * C + map.c0) / V];
     #pragma unroll
     for (int i = 0; i < V; ++i) {
       float d = bn_tof<T>(dv[i]);
@@ -383,62 +381,57 @@ __global__ __launch_bounds__(kT) void bn_bwd_reduce_kernel(
 
   __shared__ float lds[kT * BnVec<T>::V];
   const long nbC = (long)gridDim.x * C;
-  for (int pass = 0; pass < 2; ++pass) {
-    #pragma unroll
-    for (int i = 0; i < V; ++i)
-      lds[threadIdx.x * V + i] = pass ? a1[i] : a0[i];
-    __syncthreads();
-    for (int s = rpb / 2; s > 0; s >>= 1) {
-      if (row_in_block < s) {
-        #pragma unroll
-        for (int i = 0; i < V; ++i)
-          lds[threadIdx.x * V + i] +=
-              lds[(threadIdx.x + s * tpr) * V + i];
-      }
-      __syncthreads();
-    }
-    if (row_in_block == 0) {
-      #pragma unroll
-      for (int i = 0; i < V; ++i)
-        partial[pass * nbC + (long)blockIdx.x * C + c0 + i] =
-            lds[threadIdx.x * V + i];
-    }
-    __syncthreads();
-  }
+  float* row = partial + (long)blockIdx.x * C + map.c0;
+  bn_block_fold<V>(lds, a0, row, map);
+  bn_block_fold<V>(lds, a1, row + nbC, map);
 }
 
 // --------------------------------------------------------------------
 // backward stage 2: fold partials -> dgamma/dbeta and the three
-// per-channel dx coefficients:
+// per-channel dx coefficients, coef = [3, C] (P, Q, S):
 //   dx = P*dy_eff + Q*x + S
 //   P = gamma*invstd
 //   Q = -P * invstd * (dxhat_sum/R)
 //   S = -P * (dsum/R) - Q * mean
 // --------------------------------------------------------------------
+__device__ __forceinline__ void bn_bwd_pqs(
+    float* __restrict__ coef, int C, int c, float dsum, float dxhat,
+    float invR, float gamma, float mean, float invstd) {
+  const float P = gamma * invstd;
+  const float Q = -P * invstd * dxhat * invR;
+  coef[c] = P;
+  coef[C + c] = Q;
+  // S = -P*dsum*invR - Q*mean with Q*mean the fused product: spelled
+  // out, because left to contraction the compiler may fuse the other
+  // product instead, and dx would differ in its last bit
+  coef[2 * C + c] = fmaf(-mean, Q, -P * dsum * invR);
+}
+
 __global__ void bn_bwd_coef_kernel(
     const float* __restrict__ partial2,
     const float* __restrict__ gamma, const float* __restrict__ mean,
     const float* __restrict__ invstd, float* __restrict__ dgamma,
-    float* __restrict__ dbeta, float* __restrict__ coefP,
-    float* __restrict__ coefQ, float* __restrict__ coefS, long R,
-    int C) {
+    float* __restrict__ dbeta, float* __restrict__ coef, long R, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const long b2C = (long)kB2 * C;
-  float dsum = 0.f, dxhat = 0.f;
-  #pragma unroll
-  for (int b = 0; b < kB2; ++b) {
-    dsum += partial2[(long)b * C + c];
-    dxhat += partial2[b2C + (long)b * C + c];
-  }
+  float dsum, dxhat;
+  bn_fold_b2(partial2, C, c, dsum, dxhat);
   dbeta[c] = dsum;
   dgamma[c] = dxhat;
-  const float invR = 1.f / (float)R;
-  const float P = gamma[c] * invstd[c];
-  const float Q = -P * invstd[c] * dxhat * invR;
-  coefP[c] = P;
-  coefQ[c] = Q;
-  coefS[c] = -P * dsum * invR - Q * mean[c];
+  bn_bwd_pqs(coef, C, c, dsum, dxhat, 1.f / (float)R, gamma[c], mean[c],
+             invstd[c]);
+}
+
+// bn_bwd_coef_kernel on reduced sums and the global row count;
+// dgamma/dbeta stay the caller's local sums
+__global__ void bn_sync_bwd_coef_kernel(
+    const float* __restrict__ bsums, const float* __restrict__ count,
+    const float* __restrict__ gamma, const float* __restrict__ mean,
+    const float* __restrict__ invstd, float* __restrict__ coef, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  bn_bwd_pqs(coef, C, c, bsums[c], bsums[C + c], 1.f / count[0],
+             gamma[c], mean[c], invstd[c]);
 }
 
 // --------------------------------------------------------------------
@@ -477,31 +470,6 @@ __global__ __launch_bounds__(kT) void bn_bwd_dx_kernel(
     store_vec<T, V>(dx + idx, dxv);
     if constexpr (RES) store_vec<T, V>(dres + idx, drv);
   }
-}
-
-// fold one per-thread accumulator across the rpb rows of a block that
-// share a channel slot and store the block's row of a partial plane
-// (the LDS tree of bn_stats_kernel / bn_bwd_reduce_kernel)
-template <int V>
-__device__ __forceinline__ void bn_block_fold(
-    float* __restrict__ lds, const float (&a)[V],
-    float* __restrict__ plane_row, int tpr, int rpb, int row_in_block) {
-  #pragma unroll
-  for (int i = 0; i < V; ++i) lds[threadIdx.x * V + i] = a[i];
-  __syncthreads();
-  for (int s = rpb / 2; s > 0; s >>= 1) {
-    if (row_in_block < s) {
-      #pragma unroll
-      for (int i = 0; i < V; ++i)
-        lds[threadIdx.x * V + i] += lds[(threadIdx.x + s * tpr) * V + i];
-    }
-    __syncthreads();
-  }
-  if (row_in_block == 0) {
-    #pragma unroll
-    for (int i = 0; i < V; ++i) plane_row[i] = lds[threadIdx.x * V + i];
-  }
-  __syncthreads();
 }
 
 // ====================================================================
@@ -625,21 +593,17 @@ __global__ __launch_bounds__(kT) void bn_pool_bwd_reduce_kernel(
     const float* __restrict__ invstd, float* __restrict__ partial,
     long R, int H, int W, int OH, int OW, int C) {
   constexpr int V = BnVec<T>::V;
-  const int tpr = C / V;
-  const int rpb = kT / tpr;
-  const int slot = threadIdx.x % tpr;
-  const int row_in_block = threadIdx.x / tpr;
-  const int c0 = slot * V;
+  const BnRowMap<V> map(C);
 
   float mu[V], is[V];
-  load_coef<V>(mu, mean + c0);
-  load_coef<V>(is, invstd + c0);
+  load_coef<V>(mu, mean + map.c0);
+  load_coef<V>(is, invstd + map.c0);
   float a0[V], a1[V];
   #pragma unroll
   for (int i = 0; i < V; ++i) { a0[i] = 0.f; a1[i] = 0.f; }
 
-  const long row_stride = (long)gridDim.x * rpb;
-  long r = (long)blockIdx.x * rpb + row_in_block;
+  const long row_stride = (long)gridDim.x * map.rpb;
+  long r = (long)blockIdx.x * map.rpb + map.row_in_block;
   int w = (int)(r % W);
   int h = (int)((r / W) % H);
   long n = r / W / H;
@@ -648,10 +612,10 @@ __global__ __launch_bounds__(kT) void bn_pool_bwd_reduce_kernel(
   const long dn = row_stride / W / H;
   for (; r < R; r += row_stride) {
     T xv[V];
-    load_vec<T, V>(xv, x + r * C + c0);
+    load_vec<T, V>(xv, x + r * C + map.c0);
     float d[V];
     bn_pool_gather_dy<T>(d, dpool, code, n * OH * OW, h, w, OH, OW, C,
-                         tpr, slot);
+                         map.tpr, map.slot);
     #pragma unroll
     for (int i = 0; i < V; ++i) {
       const float xh = (bn_tof<T>(xv[i]) - mu[i]) * is[i];
@@ -668,9 +632,9 @@ __global__ __launch_bounds__(kT) void bn_pool_bwd_reduce_kernel(
 
   __shared__ float lds[kT * BnVec<T>::V];
   const long nbC = (long)gridDim.x * C;
-  float* row = partial + (long)blockIdx.x * C + c0;
-  bn_block_fold<V>(lds, a0, row, tpr, rpb, row_in_block);
-  bn_block_fold<V>(lds, a1, row + nbC, tpr, rpb, row_in_block);
+  float* row = partial + (long)blockIdx.x * C + map.c0;
+  bn_block_fold<V>(lds, a0, row, map);
+  bn_block_fold<V>(lds, a1, row + nbC, map);
 }
 
 // backward dx over the stem input: dx = P*dy_eff + Q*x + S
@@ -682,27 +646,22 @@ __global__ __launch_bounds__(kT) void bn_pool_bwd_dx_kernel(
     T* __restrict__ dx, int lines, int H, int W, int OH, int OW,
     int C) {
   constexpr int V = BnVec<T>::V;
-  const int tpr = C / V;
-  const int rpb = kT / tpr;
-  const int slot = threadIdx.x % tpr;
-  const int row_in_block = threadIdx.x / tpr;
-  const int c0 = slot * V;
-  if (row_in_block >= rpb) return;  // C/V not a divisor of kT
+  const BnRowMap<V> map(C);  // rows of a block: pixels of one line
   float P[V], Q[V], S[V];
-  load_coef<V>(P, coefP + c0);
-  load_coef<V>(Q, coefQ + c0);
-  load_coef<V>(S, coefS + c0);
+  load_coef<V>(P, coefP + map.c0);
+  load_coef<V>(Q, coefQ + map.c0);
+  load_coef<V>(S, coefS + map.c0);
   for (int line = blockIdx.x; line < lines; line += gridDim.x) {
     const int n = line / H;
     const int h = line - n * H;
     const long obase = (long)n * OH * OW;
-    for (int w = row_in_block; w < W; w += rpb) {
-      const long idx = ((long)line * W + w) * C + c0;
+    for (int w = map.row_in_block; w < W; w += map.rpb) {
+      const long idx = ((long)line * W + w) * C + map.c0;
       T xv[V];
       load_vec<T, V>(xv, x + idx);
       float d[V];
-      bn_pool_gather_dy<T>(d, dpool, code, obase, h, w, OH, OW, C, tpr,
-                           slot);
+      bn_pool_gather_dy<T>(d, dpool, code, obase, h, w, OH, OW, C,
+                           map.tpr, map.slot);
       T dxv[V];
       #pragma unroll
       for (int i = 0; i < V; ++i)
@@ -770,29 +729,25 @@ __global__ __launch_bounds__(kT) void bn_dual_bwd_reduce_kernel(
     const float* __restrict__ meand, const float* __restrict__ invstdd,
     float* __restrict__ partial, long R, int C) {
   constexpr int V = BnVec<T>::V;
-  const int tpr = C / V;
-  const int rpb = kT / tpr;
-  const int slot = threadIdx.x % tpr;
-  const int row_in_block = threadIdx.x / tpr;
-  const int c0 = slot * V;
+  const BnRowMap<V> map(C);
 
   float mu3[V], is3[V], mud[V], isd[V];
-  load_coef<V>(mu3, mean3 + c0);
-  load_coef<V>(is3, invstd3 + c0);
-  load_coef<V>(mud, meand + c0);
-  load_coef<V>(isd, invstdd + c0);
+  load_coef<V>(mu3, mean3 + map.c0);
+  load_coef<V>(is3, invstd3 + map.c0);
+  load_coef<V>(mud, meand + map.c0);
+  load_coef<V>(isd, invstdd + map.c0);
   float a0[V], a3[V], ad[V];
   #pragma unroll
   for (int i = 0; i < V; ++i) { a0[i] = 0.f; a3[i] = 0.f; ad[i] = 0.f; }
 
-  const long row_stride = (long)gridDim.x * rpb;
-  for (long r = (long)blockIdx.x * rpb + row_in_block; r < R;
+  const long row_stride = (long)gridDim.x * map.rpb;
+  for (long r = (long)blockIdx.x * map.rpb + map.row_in_block; r < R;
        r += row_stride) {
     T dv[V], av[V], bv[V];
-    load_vec<T, V>(dv, dy + r * C + c0);
-    load_vec<T, V>(av, x3 + r * C + c0);
-    load_vec<T, V>(bv, xd + r * C + c0);
-    const unsigned int m = mask[(r * C + c0) / V];
+    load_vec<T, V>(dv, dy + r * C + map.c0);
+    load_vec<T, V>(av, x3 + r * C + map.c0);
+    load_vec<T, V>(bv, xd + r * C + map.c0);
+    const unsigned int m = mask[(r * C + map.c0) / V];
     #pragma unroll
     for (int i = 0; i < V; ++i) {
       const float d = (m >> i) & 1u ? bn_tof<T>(dv[i]) : 0.f;
@@ -804,11 +759,11 @@ __global__ __launch_bounds__(kT) void bn_dual_bwd_reduce_kernel(
 
   __shared__ float lds[kT * BnVec<T>::V];
   const long nbC = (long)gridDim.x * C;
-  float* row = partial + (long)blockIdx.x * C + c0;
-  bn_block_fold<V>(lds, a0, row, tpr, rpb, row_in_block);
-  bn_block_fold<V>(lds, a3, row + nbC, tpr, rpb, row_in_block);
-  bn_block_fold<V>(lds, a0, row + 2 * nbC, tpr, rpb, row_in_block);
-  bn_block_fold<V>(lds, ad, row + 3 * nbC, tpr, rpb, row_in_block);
+  float* row = partial + (long)blockIdx.x * C + map.c0;
+  bn_block_fold<V>(lds, a0, row, map);
+  bn_block_fold<V>(lds, a3, row + nbC, map);
+  bn_block_fold<V>(lds, a0, row + 2 * nbC, map);
+  bn_block_fold<V>(lds, ad, row + 3 * nbC, map);
 }
 
 // backward dx for both BNs: dx3 = P3*d + Q3*x3 + S3, dxd likewise
@@ -853,240 +808,128 @@ __global__ __launch_bounds__(kT) void bn_dual_bwd_dx_kernel(
   }
 }
 
-int bn_grid_rows(long R, int rpb) {
-  long blocks = (R + rpb - 1) / rpb;
-  return (int)std::min<long>(std::max<long>(blocks, 1), kMaxStage1);
+// ====================================================================
+// host side. Every exported function validates all of its operands
+// (bn_check_* below) before it allocates, copies or launches; what
+// follows a check may reinterpret_cast and data_ptr<float>() freely.
+// ====================================================================
+int bn_vec_width(const torch::Tensor& x) {
+  return x.scalar_type() == at::kBFloat16 ? 8 : 4;
 }
 
-long bn_grid_elems(long nvec) {
-  long blocks = (nvec + kT - 1) / kT;
-  return std::min<long>(std::max<long>(blocks, 1), 16384);
-}
-
-// stats -> fold: the [2, kB2, C] second-level partials of sum / sumsq
-template <typename T>
-torch::Tensor bn_stats_partial2(const torch::Tensor& x,
-                                const at::TensorOptions& opts, long R,
-                                int C, hipStream_t stream) {
-  const int tpr = C / BnVec<T>::V;
-  const int rpb = kT / tpr;
-  const int nb = bn_grid_rows(R, rpb);
-  auto partial = torch::empty({2, nb, C}, opts);
-  auto partial2 = torch::empty({2, kB2, C}, opts);
-  hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(nb), dim3(kT), 0,
-                     stream,
-                     reinterpret_cast<const T*>(x.data_ptr()),
-                     partial.data_ptr<float>(), R, C);
-  CHECK_HIP_BN(hipGetLastError());
-  hipLaunchKernelGGL(bn_fold2_kernel,
-                     dim3((C + kFoldC - 1) / kFoldC, kB2), dim3(kT), 0,
-                     stream, partial.data_ptr<float>(), nb,
-                     partial2.data_ptr<float>(), C);
-  CHECK_HIP_BN(hipGetLastError());
-  return partial2;
-}
-
-// training-mode stats -> fold -> coef: batch mean/invstd, the apply
-// pass's scale/bias, and the running-stat update
-template <typename T>
-void bn_train_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
-                    const torch::Tensor& beta,
-                    torch::Tensor& running_mean,
-                    torch::Tensor& running_var, torch::Tensor& mean,
-                    torch::Tensor& invstd, torch::Tensor& scale,
-                    torch::Tensor& bias, double momentum, double eps,
-                    long R, int C, hipStream_t stream) {
-  torch::Tensor partial2 = bn_stats_partial2<T>(
-      x, gamma.options().dtype(at::kFloat), R, C, stream);
-  hipLaunchKernelGGL(bn_stats_coef_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, partial2.data_ptr<float>(),
-                     gamma.data_ptr<float>(),
-                     beta.data_ptr<float>(),
-                     running_mean.defined()
-                         ? running_mean.data_ptr<float>() : nullptr,
-                     running_var.defined()
-                         ? running_var.data_ptr<float>() : nullptr,
-                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                     scale.data_ptr<float>(), bias.data_ptr<float>(),
-                     R, C, (float)momentum, (float)eps);
-  CHECK_HIP_BN(hipGetLastError());
-}
-
-// the elementwise forward pass: y = [relu](scale*x + bias [+ res])
-template <typename T>
-void bn_launch_apply(const torch::Tensor& x, torch::Tensor& y,
-                     const torch::Tensor& scale,
-                     const torch::Tensor& bias,
-                     const c10::optional<torch::Tensor>& res,
-                     torch::Tensor& mask, bool relu, long R, int C,
-                     hipStream_t stream) {
-  const long total = R * (long)C;
-  const long grid = bn_grid_elems(total / BnVec<T>::V);
-  const T* resp = res.has_value()
-      ? reinterpret_cast<const T*>(res->data_ptr()) : nullptr;
-  unsigned char* mp = mask.defined()
-      ? mask.data_ptr<unsigned char>() : nullptr;
-  #define APPLY(RELU_, RES_, WM_)                                       \
-    hipLaunchKernelGGL((bn_apply_kernel<T, RELU_, RES_, WM_>),          \
-                       dim3(grid), dim3(kT), 0, stream,                 \
-                       reinterpret_cast<const T*>(x.data_ptr()),        \
-                       reinterpret_cast<T*>(y.data_ptr()),              \
-                       scale.data_ptr<float>(), bias.data_ptr<float>(), \
-                       resp, mp, total, C)
-  const bool wm = relu && mp != nullptr;
-  if (relu && resp) { if (wm) APPLY(true, true, true);
-                      else APPLY(true, true, false); }
-  else if (relu) { if (wm) APPLY(true, false, true);
-                   else APPLY(true, false, false); }
-  else if (resp) APPLY(false, true, false);
-  else APPLY(false, false, false);
-  #undef APPLY
-  CHECK_HIP_BN(hipGetLastError());
-}
+// runs the statement once, with T bound to x's element type
+#define BN_DISPATCH(x, ...)                                              \
+  do {                                                                   \
+    if ((x).scalar_type() == at::kBFloat16) {                            \
+      using T = __hip_bfloat16;                                          \
+      __VA_ARGS__;                                                       \
+    } else {                                                             \
+      using T = float;                                                   \
+      __VA_ARGS__;                                                       \
+    }                                                                    \
+  } while (0)
 
 template <typename T>
-void bn_fwd_impl(const torch::Tensor& x, torch::Tensor& y,
-                 const torch::Tensor& gamma, const torch::Tensor& beta,
-                 torch::Tensor& running_mean, torch::Tensor& running_var,
-                 torch::Tensor& mean, torch::Tensor& invstd,
-                 const c10::optional<torch::Tensor>& res,
-                 torch::Tensor& mask, bool relu,
-                 bool training, double momentum, double eps, long R,
-                 int C, hipStream_t stream) {
-  auto opts = gamma.options().dtype(at::kFloat);
-  auto scale = torch::empty({C}, opts);
-  auto bias = torch::empty({C}, opts);
-  if (training) {
-    bn_train_coefs<T>(x, gamma, beta, running_mean, running_var, mean,
-                      invstd, scale, bias, momentum, eps, R, C, stream);
-  } else {
-    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((C + 255) / 256),
-                       dim3(256), 0, stream,
-                       running_mean.data_ptr<float>(),
-                       running_var.data_ptr<float>(),
-                       gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                       scale.data_ptr<float>(), bias.data_ptr<float>(),
-                       C, (float)eps);
-    CHECK_HIP_BN(hipGetLastError());
+T* bn_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<T*>(t.data_ptr());
+}
+
+float* fptr(const torch::Tensor& t) { return t.data_ptr<float>(); }
+
+// "no running stats" reaches us as an undefined or an empty tensor
+bool bn_absent(const torch::Tensor& t) {
+  return !t.defined() || t.numel() == 0;
+}
+float* bn_running_ptr(const torch::Tensor& t) {
+  return bn_absent(t) ? nullptr : fptr(t);
+}
+
+struct BnDims { int C, V; long R; };
+
+// the activation: 4-D channels_last bf16/fp32 on the GPU, non-empty,
+// C/V a power of two <= kT (see BnRowMap)
+BnDims bn_check_input(const torch::Tensor& x, const char* what) {
+  TORCH_CHECK(x.defined() && x.is_cuda() && x.dim() == 4, what,
+              ": 4-D GPU input expected");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 ||
+              x.scalar_type() == at::kFloat, what,
+              ": dtype must be bf16 or f32");
+  TORCH_CHECK(x.numel() > 0, what, ": empty input");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), what,
+              ": channels_last input required");
+  const int C = (int)x.size(1);
+  const int V = bn_vec_width(x);
+  TORCH_CHECK(C % V == 0 && C / V <= kT, what, ": C=", C,
+              " unsupported for vec", V);
+  const int tpr = C / V;
+  TORCH_CHECK((tpr & (tpr - 1)) == 0, what, ": C/", V,
+              " must be a power of two");
+  return {C, V, x.numel() / C};
+}
+
+// an fp32 vector of n elements on x's device
+void bn_check_vec(const torch::Tensor& t, const torch::Tensor& x, long n,
+                  const char* what, const char* name) {
+  TORCH_CHECK(t.defined() && t.scalar_type() == at::kFloat &&
+              t.device() == x.device() && t.is_contiguous() &&
+              t.numel() == n, what, ": ", name, " must be fp32 [", n,
+              "] on the input's device");
+}
+
+struct BnNamed { const char* name; const torch::Tensor& t; };
+
+// per-channel operands: fp32 [C] on x's device
+void bn_check_channel_vecs(const torch::Tensor& x, const char* what,
+                           std::initializer_list<BnNamed> vecs) {
+  for (const BnNamed& v : vecs) bn_check_vec(v.t, x, x.size(1), what, v.name);
+}
+
+// running stats: both or neither; `required` in eval mode
+void bn_check_running(const torch::Tensor& running_mean,
+                      const torch::Tensor& running_var,
+                      const torch::Tensor& x, bool required,
+                      const char* what) {
+  TORCH_CHECK(bn_absent(running_mean) == bn_absent(running_var), what,
+              ": running_mean and running_var go together");
+  if (bn_absent(running_mean)) {
+    TORCH_CHECK(!required, what, ": eval mode needs the running stats");
+    return;
   }
-  bn_launch_apply<T>(x, y, scale, bias, res, mask, relu, R, C, stream);
+  bn_check_channel_vecs(x, what, {{"running_mean", running_mean},
+                                  {"running_var", running_var}});
 }
 
-// backward reduce -> fold: the [2, kB2, C] second-level partials of
-// sum(dy_eff) / sum(dy_eff * xhat)
-template <typename T>
-torch::Tensor bn_bwd_partial2(const torch::Tensor& dy,
-                              const torch::Tensor& mask,
-                              const torch::Tensor& x,
-                              const torch::Tensor& mean,
-                              const torch::Tensor& invstd, bool relu,
-                              long R, int C, hipStream_t stream) {
-  const int tpr = C / BnVec<T>::V;
-  const int rpb = kT / tpr;
-  const int nb = bn_grid_rows(R, rpb);
-  auto fopts = mean.options().dtype(at::kFloat);
-  auto partial = torch::empty({2, nb, C}, fopts);
-  auto partial2 = torch::empty({2, kB2, C}, fopts);
-  const unsigned char* mp = mask.defined()
-      ? mask.data_ptr<unsigned char>() : nullptr;
-  #define RED(RELU_)                                                     \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, RELU_>), dim3(nb),       \
-                       dim3(kT), 0, stream,                              \
-                       reinterpret_cast<const T*>(dy.data_ptr()),        \
-                       mp,                                               \
-                       reinterpret_cast<const T*>(x.data_ptr()),         \
-                       mean.data_ptr<float>(), invstd.data_ptr<float>(), \
-                       partial.data_ptr<float>(), R, C)
-  if (relu) RED(true); else RED(false);
-  #undef RED
-  CHECK_HIP_BN(hipGetLastError());
-  hipLaunchKernelGGL(bn_fold2_kernel,
-                     dim3((C + kFoldC - 1) / kFoldC, kB2), dim3(kT), 0,
-                     stream, partial.data_ptr<float>(), nb,
-                     partial2.data_ptr<float>(), C);
-  CHECK_HIP_BN(hipGetLastError());
-  return partial2;
+// a second activation (residual, other input, gradient): x's sizes,
+// dtype and device; channels_last too unless the caller converts it
+void bn_check_like(const torch::Tensor& t, const torch::Tensor& x,
+                   bool nhwc, const char* what, const char* msg) {
+  TORCH_CHECK(t.defined() && t.sizes() == x.sizes() &&
+              t.scalar_type() == x.scalar_type() &&
+              t.device() == x.device() &&
+              (!nhwc || t.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              what, ": ", msg);
 }
 
-// the elementwise backward pass: dx = P*dy_eff + Q*x + S [, dres]
-template <typename T>
-void bn_launch_bwd_dx(const torch::Tensor& dy, const torch::Tensor& mask,
-                      const torch::Tensor& x, const torch::Tensor& coefP,
-                      const torch::Tensor& coefQ,
-                      const torch::Tensor& coefS, torch::Tensor& dx,
-                      const c10::optional<torch::Tensor>& dres, bool relu,
-                      long R, int C, hipStream_t stream) {
-  const unsigned char* mp = mask.defined()
-      ? mask.data_ptr<unsigned char>() : nullptr;
-  const long total = R * (long)C;
-  const long grid = bn_grid_elems(total / BnVec<T>::V);
-  T* dresp = dres.has_value()
-      ? reinterpret_cast<T*>(dres->data_ptr()) : nullptr;
-  #define DX(RELU_, RES_)                                                \
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<T, RELU_, RES_>), dim3(grid),   \
-                       dim3(kT), 0, stream,                              \
-                       reinterpret_cast<const T*>(dy.data_ptr()),        \
-                       mp,                                               \
-                       reinterpret_cast<const T*>(x.data_ptr()),         \
-                       coefP.data_ptr<float>(), coefQ.data_ptr<float>(), \
-                       coefS.data_ptr<float>(),                          \
-                       reinterpret_cast<T*>(dx.data_ptr()), dresp,       \
-                       total, C)
-  if (relu && dresp) DX(true, true);
-  else if (relu) DX(true, false);
-  else if (dresp) DX(false, true);
-  else DX(false, false);
-  #undef DX
-  CHECK_HIP_BN(hipGetLastError());
+// the forward's ReLU bitmask: one byte per V elements
+void bn_check_mask(const torch::Tensor& mask, const torch::Tensor& x,
+                   const char* what) {
+  TORCH_CHECK(mask.defined() && mask.scalar_type() == at::kByte &&
+              mask.device() == x.device() && mask.is_contiguous() &&
+              mask.numel() == x.numel() / bn_vec_width(x),
+              what, ": relu path needs the fwd mask");
 }
 
-template <typename T>
-void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& mask,
-                 const torch::Tensor& x, const torch::Tensor& mean,
-                 const torch::Tensor& invstd, const torch::Tensor& gamma,
-                 torch::Tensor& dx, torch::Tensor& dgamma,
-                 torch::Tensor& dbeta,
-                 const c10::optional<torch::Tensor>& dres, bool relu,
-                 long R, int C, hipStream_t stream) {
-  auto fopts = gamma.options().dtype(at::kFloat);
-  torch::Tensor partial2 = bn_bwd_partial2<T>(dy, mask, x, mean, invstd,
-                                              relu, R, C, stream);
-  auto coefP = torch::empty({C}, fopts);
-  auto coefQ = torch::empty({C}, fopts);
-  auto coefS = torch::empty({C}, fopts);
-  hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, partial2.data_ptr<float>(),
-                     gamma.data_ptr<float>(), mean.data_ptr<float>(),
-                     invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                     dbeta.data_ptr<float>(), coefP.data_ptr<float>(),
-                     coefQ.data_ptr<float>(), coefS.data_ptr<float>(), R,
-                     C);
-  CHECK_HIP_BN(hipGetLastError());
-  bn_launch_bwd_dx<T>(dy, mask, x, coefP, coefQ, coefS, dx, dres, relu, R,
-                      C, stream);
-}
-
-// backward fold -> coef for one BN from its [2, nb, C] partial:
-// dgamma/dbeta and coef = [3, C] (P, Q, S)
-void bn_bwd_fold_coefs(const float* partial, int nb,
-                       const torch::Tensor& gamma,
-                       const torch::Tensor& mean,
-                       const torch::Tensor& invstd, torch::Tensor& dgamma,
-                       torch::Tensor& dbeta, torch::Tensor& coef, long R,
-                       int C, hipStream_t stream) {
-  auto partial2 = torch::empty({2, kB2, C}, coef.options());
-  hipLaunchKernelGGL(bn_fold2_kernel,
-                     dim3((C + kFoldC - 1) / kFoldC, kB2), dim3(kT), 0,
-                     stream, partial, nb, partial2.data_ptr<float>(), C);
-  CHECK_HIP_BN(hipGetLastError());
-  float* cp = coef.data_ptr<float>();
-  hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, partial2.data_ptr<float>(),
-                     gamma.data_ptr<float>(), mean.data_ptr<float>(),
-                     invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                     dbeta.data_ptr<float>(), cp, cp + C, cp + 2 * C, R,
-                     C);
-  CHECK_HIP_BN(hipGetLastError());
+// what every backward shares: x, the gradient, the saved statistics
+// and, with ReLU, the mask
+BnDims bn_check_bwd_args(const torch::Tensor& dy, const torch::Tensor& mask,
+                         const torch::Tensor& x, const torch::Tensor& mean,
+                         const torch::Tensor& invstd, bool relu,
+                         const char* what) {
+  const BnDims d = bn_check_input(x, what);
+  bn_check_like(dy, x, false, what, "bad gradient");
+  bn_check_channel_vecs(x, what, {{"mean", mean}, {"invstd", invstd}});
+  if (relu) bn_check_mask(mask, x, what);
+  return d;
 }
 
 struct PoolGeom { int N, H, W, OH, OW; };
@@ -1099,201 +942,263 @@ PoolGeom pool_geom(const torch::Tensor& x) {
   return g;
 }
 
-template <typename T>
-void bn_relu_pool_fwd_impl(const torch::Tensor& x, torch::Tensor& pooled,
-                           torch::Tensor& code,
-                           const torch::Tensor& gamma,
-                           const torch::Tensor& beta,
-                           torch::Tensor& running_mean,
-                           torch::Tensor& running_var,
-                           torch::Tensor& mean, torch::Tensor& invstd,
-                           double momentum, double eps, long R, int C,
-                           hipStream_t stream) {
-  auto opts = gamma.options().dtype(at::kFloat);
-  auto scale = torch::empty({C}, opts);
-  auto bias = torch::empty({C}, opts);
-  bn_train_coefs<T>(x, gamma, beta, running_mean, running_var, mean,
-                    invstd, scale, bias, momentum, eps, R, C, stream);
-  const PoolGeom g = pool_geom(x);
-  const long nvec = code.numel();
-  hipLaunchKernelGGL((bn_relu_pool_apply_kernel<T>),
-                     dim3(bn_grid_elems(nvec)), dim3(kT), 0, stream,
-                     reinterpret_cast<const T*>(x.data_ptr()),
-                     reinterpret_cast<T*>(pooled.data_ptr()),
-                     reinterpret_cast<unsigned int*>(code.data_ptr()),
-                     scale.data_ptr<float>(), bias.data_ptr<float>(),
-                     (unsigned int)nvec, g.H, g.W, g.OH, g.OW, C);
+// the stem input: the pool kernels index pixels and code words in 32 bits
+BnDims bn_check_pool_input(const torch::Tensor& x, const char* what) {
+  const BnDims d = bn_check_input(x, what);
+  TORCH_CHECK(x.numel() < (1L << 31), what, ": input too large");
+  return d;
+}
+
+// ---- launches ------------------------------------------------------
+int bn_stage1_blocks(const BnDims& d) {
+  const int rpb = kT / (d.C / d.V);
+  const long blocks = (d.R + rpb - 1) / rpb;
+  return (int)std::min<long>(std::max<long>(blocks, 1), kMaxStage1);
+}
+
+long bn_grid_elems(long nvec) {
+  long blocks = (nvec + kT - 1) / kT;
+  return std::min<long>(std::max<long>(blocks, 1), 16384);
+}
+
+dim3 bn_grid_channels(int C) { return dim3((C + 255) / 256); }
+
+at::TensorOptions bn_fopts(const torch::Tensor& x) {
+  return x.options().dtype(at::kFloat);
+}
+
+// stage 2a: one [2, nb, C] stage-1 partial -> [2, kB2, C]
+torch::Tensor bn_fold2(const float* partial, int nb, const torch::Tensor& x,
+                       hipStream_t stream) {
+  const int C = (int)x.size(1);
+  auto partial2 = torch::empty({2, kB2, C}, bn_fopts(x));
+  hipLaunchKernelGGL(bn_fold2_kernel,
+                     dim3((C + kFoldC - 1) / kFoldC, kB2), dim3(kT), 0,
+                     stream, partial, nb, fptr(partial2), C);
+  CHECK_HIP_BN(hipGetLastError());
+  return partial2;
+}
+
+// stats -> fold: the [2, kB2, C] second-level partials of sum / sumsq
+torch::Tensor bn_stats_partial2(const torch::Tensor& x, const BnDims& d,
+                                hipStream_t stream) {
+  const int nb = bn_stage1_blocks(d);
+  auto partial = torch::empty({2, nb, d.C}, bn_fopts(x));
+  BN_DISPATCH(x, hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(nb),
+                                    dim3(kT), 0, stream, bn_ptr<const T>(x),
+                                    fptr(partial), d.R, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  return bn_fold2(fptr(partial), nb, x, stream);
+}
+
+// the per-channel results every forward returns or hands to its
+// elementwise pass
+struct BnFwdOut {
+  torch::Tensor mean, invstd, scale, bias;
+  explicit BnFwdOut(const torch::Tensor& x) {
+    for (torch::Tensor* t : {&mean, &invstd, &scale, &bias})
+      *t = torch::empty({x.size(1)}, bn_fopts(x));
+  }
+  BnFwdCoef args(const torch::Tensor& gamma, const torch::Tensor& beta,
+                 const torch::Tensor& running_mean,
+                 const torch::Tensor& running_var, double momentum,
+                 double eps) const {
+    return {fptr(gamma), fptr(beta), bn_running_ptr(running_mean),
+            bn_running_ptr(running_var), fptr(mean), fptr(invstd),
+            fptr(scale), fptr(bias), (float)momentum, (float)eps};
+  }
+};
+
+// training-mode stats -> fold -> coef: batch mean/invstd, the apply
+// pass's scale/bias, and the running-stat update
+BnFwdOut bn_train_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
+                        const torch::Tensor& beta,
+                        const torch::Tensor& running_mean,
+                        const torch::Tensor& running_var, double momentum,
+                        double eps, const BnDims& d, hipStream_t stream) {
+  BnFwdOut o(x);
+  torch::Tensor partial2 = bn_stats_partial2(x, d, stream);
+  hipLaunchKernelGGL(bn_stats_coef_kernel, bn_grid_channels(d.C),
+                     dim3(256), 0, stream, fptr(partial2),
+                     o.args(gamma, beta, running_mean, running_var,
+                            momentum, eps), d.R, d.C);
+  CHECK_HIP_BN(hipGetLastError());
+  return o;
+}
+
+// eval mode: scale/bias straight from the running stats; mean and
+// invstd are returned unset
+BnFwdOut bn_eval_coefs(const torch::Tensor& x, const torch::Tensor& gamma,
+                       const torch::Tensor& beta,
+                       const torch::Tensor& running_mean,
+                       const torch::Tensor& running_var, double eps,
+                       const BnDims& d, hipStream_t stream) {
+  BnFwdOut o(x);
+  hipLaunchKernelGGL(bn_eval_coef_kernel, bn_grid_channels(d.C), dim3(256),
+                     0, stream, fptr(running_mean), fptr(running_var),
+                     fptr(gamma), fptr(beta), fptr(o.scale), fptr(o.bias),
+                     d.C, (float)eps);
+  CHECK_HIP_BN(hipGetLastError());
+  return o;
+}
+
+// the elementwise forward pass: y = [relu](scale*x + bias [+ res]);
+// the mask is written when one is given
+void bn_launch_apply(const torch::Tensor& x, torch::Tensor& y,
+                     const BnFwdOut& o,
+                     const c10::optional<torch::Tensor>& res,
+                     const torch::Tensor& mask, bool relu, const BnDims& d,
+                     hipStream_t stream) {
+  const long total = d.R * (long)d.C;
+  const long grid = bn_grid_elems(total / d.V);
+  unsigned char* mp = mask.defined()
+      ? mask.data_ptr<unsigned char>() : nullptr;
+  const bool wm = relu && mp != nullptr;
+  #define APPLY(RELU_, RES_, WM_)                                       \
+    hipLaunchKernelGGL((bn_apply_kernel<T, RELU_, RES_, WM_>),          \
+                       dim3(grid), dim3(kT), 0, stream,                 \
+                       bn_ptr<const T>(x), bn_ptr<T>(y), fptr(o.scale), \
+                       fptr(o.bias), resp, mp, total, d.C)
+  BN_DISPATCH(x, {
+    const T* resp = res.has_value() ? bn_ptr<const T>(*res) : nullptr;
+    if (relu && resp) { if (wm) APPLY(true, true, true);
+                        else APPLY(true, true, false); }
+    else if (relu) { if (wm) APPLY(true, false, true);
+                     else APPLY(true, false, false); }
+    else if (resp) APPLY(false, true, false);
+    else APPLY(false, false, false);
+  });
+  #undef APPLY
   CHECK_HIP_BN(hipGetLastError());
 }
 
-template <typename T>
-void bn_relu_pool_bwd_impl(const torch::Tensor& dpool,
-                           const torch::Tensor& code,
+// backward reduce -> fold: the [2, kB2, C] second-level partials of
+// sum(dy_eff) / sum(dy_eff * xhat)
+torch::Tensor bn_bwd_partial(const torch::Tensor& dy,
+                             const torch::Tensor& mask,
+                             const torch::Tensor& x,
+                             const torch::Tensor& mean,
+                             const torch::Tensor& invstd, bool relu,
+                             const BnDims& d, hipStream_t stream) {
+  const int nb = bn_stage1_blocks(d);
+  auto partial = torch::empty({2, nb, d.C}, bn_fopts(x));
+  const unsigned char* mp = relu ? mask.data_ptr<unsigned char>() : nullptr;
+  #define RED(RELU_)                                                     \
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, RELU_>), dim3(nb),       \
+                       dim3(kT), 0, stream, bn_ptr<const T>(dy), mp,     \
+                       bn_ptr<const T>(x), fptr(mean), fptr(invstd),     \
+                       fptr(partial), d.R, d.C)
+  BN_DISPATCH(x, { if (relu) RED(true); else RED(false); });
+  #undef RED
+  CHECK_HIP_BN(hipGetLastError());
+  return partial;
+}
+
+// backward fold -> coef for one BN from its [2, nb, C] stage-1 partial:
+// dgamma, dbeta and coef = [3, C] (P, Q, S)
+struct BnBwdOut { torch::Tensor dgamma, dbeta, coef; };
+
+BnBwdOut bn_bwd_fold_coefs(const float* partial, int nb,
                            const torch::Tensor& x,
+                           const torch::Tensor& gamma,
                            const torch::Tensor& mean,
-                           const torch::Tensor& invstd,
-                           const torch::Tensor& gamma, torch::Tensor& dx,
-                           torch::Tensor& dgamma, torch::Tensor& dbeta,
-                           long R, int C, hipStream_t stream) {
-  const PoolGeom g = pool_geom(x);
-  const int lines = g.N * g.H;
-  const int nb = bn_grid_rows(R, kT / (C / BnVec<T>::V));
-  auto fopts = gamma.options().dtype(at::kFloat);
-  auto partial = torch::empty({2, nb, C}, fopts);
-  auto coef = torch::empty({3, C}, fopts);
-  const T* dp = reinterpret_cast<const T*>(dpool.data_ptr());
-  const unsigned int* cp =
-      reinterpret_cast<const unsigned int*>(code.data_ptr());
-  const T* xp = reinterpret_cast<const T*>(x.data_ptr());
-  hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<T>), dim3(nb), dim3(kT),
-                     0, stream, dp, cp, xp, mean.data_ptr<float>(),
-                     invstd.data_ptr<float>(), partial.data_ptr<float>(),
-                     R, g.H, g.W, g.OH, g.OW, C);
+                           const torch::Tensor& invstd, const BnDims& d,
+                           hipStream_t stream) {
+  BnBwdOut o = {torch::empty({d.C}, bn_fopts(x)),
+                torch::empty({d.C}, bn_fopts(x)),
+                torch::empty({3, d.C}, bn_fopts(x))};
+  torch::Tensor partial2 = bn_fold2(partial, nb, x, stream);
+  hipLaunchKernelGGL(bn_bwd_coef_kernel, bn_grid_channels(d.C), dim3(256),
+                     0, stream, fptr(partial2), fptr(gamma), fptr(mean),
+                     fptr(invstd), fptr(o.dgamma), fptr(o.dbeta),
+                     fptr(o.coef), d.R, d.C);
   CHECK_HIP_BN(hipGetLastError());
-  bn_bwd_fold_coefs(partial.data_ptr<float>(), nb, gamma, mean, invstd,
-                    dgamma, dbeta, coef, R, C, stream);
-  const float* cf = coef.data_ptr<float>();
-  hipLaunchKernelGGL((bn_pool_bwd_dx_kernel<T>),
-                     dim3(std::min(lines, 16384)), dim3(kT), 0, stream,
-                     dp, cp, xp, cf, cf + C, cf + 2 * C,
-                     reinterpret_cast<T*>(dx.data_ptr()), lines, g.H,
-                     g.W, g.OH, g.OW, C);
+  return o;
+}
+
+// the elementwise backward pass: dx = P*dy_eff + Q*x + S [, dres];
+// coef = [3, C]
+void bn_launch_bwd_dx(const torch::Tensor& dy, const torch::Tensor& mask,
+                      const torch::Tensor& x, const torch::Tensor& coef,
+                      torch::Tensor& dx,
+                      const c10::optional<torch::Tensor>& dres, bool relu,
+                      const BnDims& d, hipStream_t stream) {
+  const unsigned char* mp = relu ? mask.data_ptr<unsigned char>() : nullptr;
+  const long total = d.R * (long)d.C;
+  const long grid = bn_grid_elems(total / d.V);
+  const float* cf = fptr(coef);
+  #define DX(RELU_, RES_)                                                \
+    hipLaunchKernelGGL((bn_bwd_dx_kernel<T, RELU_, RES_>), dim3(grid),   \
+                       dim3(kT), 0, stream, bn_ptr<const T>(dy), mp,     \
+                       bn_ptr<const T>(x), cf, cf + d.C, cf + 2 * d.C,   \
+                       bn_ptr<T>(dx), dresp, total, d.C)
+  BN_DISPATCH(x, {
+    T* dresp = dres.has_value() ? bn_ptr<T>(*dres) : nullptr;
+    if (relu && dresp) DX(true, true);
+    else if (relu) DX(true, false);
+    else if (dresp) DX(false, true);
+    else DX(false, false);
+  });
+  #undef DX
   CHECK_HIP_BN(hipGetLastError());
-}
-
-template <typename T>
-void bn_dual_fwd_impl(const torch::Tensor& x3, const torch::Tensor& xd,
-                      torch::Tensor& y, torch::Tensor& mask,
-                      const torch::Tensor& gamma3,
-                      const torch::Tensor& beta3, torch::Tensor& rm3,
-                      torch::Tensor& rv3, const torch::Tensor& gammad,
-                      const torch::Tensor& betad, torch::Tensor& rmd,
-                      torch::Tensor& rvd, torch::Tensor& mean3,
-                      torch::Tensor& invstd3, torch::Tensor& meand,
-                      torch::Tensor& invstdd, double momentum3,
-                      double momentumd, double eps3, double epsd, long R,
-                      int C, hipStream_t stream) {
-  auto opts = gamma3.options().dtype(at::kFloat);
-  auto scale3 = torch::empty({C}, opts);
-  auto bias3 = torch::empty({C}, opts);
-  auto scaled = torch::empty({C}, opts);
-  auto biasd = torch::empty({C}, opts);
-  bn_train_coefs<T>(xd, gammad, betad, rmd, rvd, meand, invstdd, scaled,
-                    biasd, momentumd, epsd, R, C, stream);
-  bn_train_coefs<T>(x3, gamma3, beta3, rm3, rv3, mean3, invstd3, scale3,
-                    bias3, momentum3, eps3, R, C, stream);
-  const long total = R * (long)C;
-  hipLaunchKernelGGL((bn_dual_apply_kernel<T>),
-                     dim3(bn_grid_elems(total / BnVec<T>::V)), dim3(kT),
-                     0, stream,
-                     reinterpret_cast<const T*>(x3.data_ptr()),
-                     reinterpret_cast<const T*>(xd.data_ptr()),
-                     reinterpret_cast<T*>(y.data_ptr()),
-                     scale3.data_ptr<float>(), bias3.data_ptr<float>(),
-                     scaled.data_ptr<float>(), biasd.data_ptr<float>(),
-                     mask.data_ptr<unsigned char>(), total, C);
-  CHECK_HIP_BN(hipGetLastError());
-}
-
-template <typename T>
-void bn_dual_bwd_impl(const torch::Tensor& dy, const torch::Tensor& mask,
-                      const torch::Tensor& x3, const torch::Tensor& xd,
-                      const torch::Tensor& mean3,
-                      const torch::Tensor& invstd3,
-                      const torch::Tensor& gamma3,
-                      const torch::Tensor& meand,
-                      const torch::Tensor& invstdd,
-                      const torch::Tensor& gammad,
-                      std::vector<torch::Tensor>& out, long R, int C,
-                      hipStream_t stream) {
-  // out: dx3, dxd, dgamma3, dbeta3, dgammad, dbetad
-  const int tpr = C / BnVec<T>::V;
-  const int rpb = kT / tpr;
-  const int nb = bn_grid_rows(R, rpb);
-  auto fopts = gamma3.options().dtype(at::kFloat);
-  auto partial = torch::empty({4, nb, C}, fopts);
-  auto coef3 = torch::empty({3, C}, fopts);
-  auto coefd = torch::empty({3, C}, fopts);
-  const T* dyp = reinterpret_cast<const T*>(dy.data_ptr());
-  const unsigned char* mp = mask.data_ptr<unsigned char>();
-  const T* x3p = reinterpret_cast<const T*>(x3.data_ptr());
-  const T* xdp = reinterpret_cast<const T*>(xd.data_ptr());
-  hipLaunchKernelGGL((bn_dual_bwd_reduce_kernel<T>), dim3(nb), dim3(kT),
-                     0, stream, dyp, mp, x3p, xdp,
-                     mean3.data_ptr<float>(), invstd3.data_ptr<float>(),
-                     meand.data_ptr<float>(), invstdd.data_ptr<float>(),
-                     partial.data_ptr<float>(), R, C);
-  CHECK_HIP_BN(hipGetLastError());
-  const float* pp = partial.data_ptr<float>();
-  bn_bwd_fold_coefs(pp, nb, gamma3, mean3, invstd3, out[2], out[3],
-                    coef3, R, C, stream);
-  bn_bwd_fold_coefs(pp + 2 * (long)nb * C, nb, gammad, meand, invstdd,
-                    out[4], out[5], coefd, R, C, stream);
-  const long total = R * (long)C;
-  hipLaunchKernelGGL((bn_dual_bwd_dx_kernel<T>),
-                     dim3(bn_grid_elems(total / BnVec<T>::V)), dim3(kT),
-                     0, stream, dyp, mp, x3p, xdp,
-                     coef3.data_ptr<float>(), coefd.data_ptr<float>(),
-                     reinterpret_cast<T*>(out[0].data_ptr()),
-                     reinterpret_cast<T*>(out[1].data_ptr()), total, C);
-  CHECK_HIP_BN(hipGetLastError());
-}
-
-void bn_check_input(const torch::Tensor& x, const char* what) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4, what,
-              ": 4-D GPU input expected");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), what,
-              ": channels_last input required");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 ||
-              x.scalar_type() == at::kFloat, what,
-              ": dtype must be bf16 or f32");
-  const int C = (int)x.size(1);
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  TORCH_CHECK(C % V == 0 && C / V <= kT, what, ": C=", C,
-              " unsupported for vec", V);
-}
-
-// The sync entry points additionally want C/V to be a power of two:
-// only then do the LDS trees of the stage-1 reductions cover every row
-// of a block.
-void bn_check_sync_input(const torch::Tensor& x, const char* what) {
-  bn_check_input(x, what);
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  const int tpr = (int)x.size(1) / V;
-  TORCH_CHECK((tpr & (tpr - 1)) == 0, what, ": C/", V,
-              " must be a power of two");
-  TORCH_CHECK(x.numel() > 0, what, ": empty input");
-}
-
-// an fp32 vector of n elements on x's device
-void bn_check_vec(const torch::Tensor& t, const torch::Tensor& x, long n,
-                  const char* what, const char* name) {
-  TORCH_CHECK(t.defined() && t.scalar_type() == at::kFloat &&
-              t.device() == x.device() && t.is_contiguous() &&
-              t.numel() == n, what, ": ", name, " must be fp32 [", n,
-              "] on the input's device");
-}
-
-void bn_check_bwd_args(const torch::Tensor& dy, const torch::Tensor& mask,
-                       const torch::Tensor& x, const torch::Tensor& mean,
-                       const torch::Tensor& invstd, bool relu,
-                       const char* what) {
-  bn_check_sync_input(x, what);
-  const int C = (int)x.size(1);
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  TORCH_CHECK(dy.sizes() == x.sizes() &&
-              dy.scalar_type() == x.scalar_type() &&
-              dy.device() == x.device(), what, ": bad gradient");
-  bn_check_vec(mean, x, C, what, "mean");
-  bn_check_vec(invstd, x, C, what, "invstd");
-  TORCH_CHECK(!relu || (mask.defined() &&
-                        mask.scalar_type() == at::kByte &&
-                        mask.device() == x.device() &&
-                        mask.numel() == x.numel() / V),
-              what, ": relu path needs the fwd mask");
 }
 
 }  // namespace
+
+// x: [N, C, H, W] channels_last (viewed as [R, C]); gamma/beta fp32;
+// the running stats may be absent in training mode.
+// Returns (y, save_mean, save_invstd, mask).
+std::vector<torch::Tensor> fused_bn_fwd(
+    torch::Tensor x, torch::Tensor gamma, torch::Tensor beta,
+    torch::Tensor running_mean, torch::Tensor running_var,
+    c10::optional<torch::Tensor> res, bool relu, bool training,
+    double momentum, double eps) {
+  const char* what = "fused_bn_fwd";
+  const BnDims d = bn_check_input(x, what);
+  bn_check_channel_vecs(x, what, {{"gamma", gamma}, {"beta", beta}});
+  bn_check_running(running_mean, running_var, x, !training, what);
+  if (res.has_value()) bn_check_like(*res, x, true, what, "bad residual");
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto y = torch::empty_like(x);  // keeps channels_last layout
+  // ReLU bitmask (1 byte per V elems) replaces re-reading y in
+  // backward: ~25% less bwd traffic
+  torch::Tensor mask;
+  if (relu && training)
+    mask = torch::empty({x.numel() / d.V}, x.options().dtype(at::kByte));
+  const BnFwdOut o = training
+      ? bn_train_coefs(x, gamma, beta, running_mean, running_var, momentum,
+                       eps, d, stream)
+      : bn_eval_coefs(x, gamma, beta, running_mean, running_var, eps, d,
+                      stream);
+  bn_launch_apply(x, y, o, res, mask, relu, d, stream);
+  if (!mask.defined())
+    mask = torch::empty({0}, x.options().dtype(at::kByte));
+  return {y, o.mean, o.invstd, mask};
+}
+
+// Returns (dx, dgamma, dbeta[, dres]). mask: ReLU bitmask from fwd
+// (empty tensor when relu=false).
+std::vector<torch::Tensor> fused_bn_bwd(
+    torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
+    torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma,
+    bool relu, bool has_res) {
+  const char* what = "fused_bn_bwd";
+  const BnDims d = bn_check_bwd_args(dy, mask, x, mean, invstd, relu, what);
+  bn_check_channel_vecs(x, what, {{"gamma", gamma}});
+  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto dx = torch::empty_like(x);
+  c10::optional<torch::Tensor> dres;
+  if (has_res) dres = torch::empty_like(x);
+  torch::Tensor partial =
+      bn_bwd_partial(dy, mask, x, mean, invstd, relu, d, stream);
+  BnBwdOut o = bn_bwd_fold_coefs(fptr(partial), (int)partial.size(1), x,
+                                 gamma, mean, invstd, d, stream);
+  bn_launch_bwd_dx(dy, mask, x, o.coef, dx, dres, relu, d, stream);
+  std::vector<torch::Tensor> out = {dx, o.dgamma, o.dbeta};
+  if (has_res) out.push_back(*dres);
+  return out;
+}
 
 // ---- synchronized BN: forward and backward cut where the sums exist.
 // No call below waits for the device or reads a value back.
@@ -1301,18 +1206,13 @@ void bn_check_bwd_args(const torch::Tensor& dy, const torch::Tensor& mask,
 // Returns sums = fp32 [2C+1]: sum(x), sum(x^2) per channel, then the
 // row count N*H*W.
 torch::Tensor fused_bn_sync_stats(torch::Tensor x) {
-  bn_check_sync_input(x, "fused_bn_sync_stats");
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
+  const BnDims d = bn_check_input(x, "fused_bn_sync_stats");
   auto stream = at::hip::getCurrentHIPStream().stream();
-  auto fopts = x.options().dtype(at::kFloat);
-  auto sums = torch::empty({2 * (long)C + 1}, fopts);
-  torch::Tensor partial2 = x.scalar_type() == at::kBFloat16
-      ? bn_stats_partial2<__hip_bfloat16>(x, fopts, R, C, stream)
-      : bn_stats_partial2<float>(x, fopts, R, C, stream);
-  hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, partial2.data_ptr<float>(),
-                     sums.data_ptr<float>(), C, (float)R, true);
+  auto sums = torch::empty({2 * (long)d.C + 1}, bn_fopts(x));
+  torch::Tensor partial2 = bn_stats_partial2(x, d, stream);
+  hipLaunchKernelGGL(bn_sync_fold_kernel, bn_grid_channels(d.C),
+                     dim3(256), 0, stream, fptr(partial2), fptr(sums),
+                     d.C, (float)d.R, true);
   CHECK_HIP_BN(hipGetLastError());
   return sums;
 }
@@ -1325,59 +1225,23 @@ std::vector<torch::Tensor> fused_bn_sync_apply(
     torch::Tensor running_var, c10::optional<torch::Tensor> res,
     bool relu, double momentum, double eps) {
   const char* what = "fused_bn_sync_apply";
-  bn_check_sync_input(x, what);
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  bn_check_vec(sums, x, 2 * (long)C + 1, what, "sums");
-  bn_check_vec(gamma, x, C, what, "gamma");
-  bn_check_vec(beta, x, C, what, "beta");
-  // an empty tensor stands for "no running stats", as in fused_bn_fwd
-  const bool has_running =
-      running_mean.defined() && running_mean.numel() > 0;
-  TORCH_CHECK(has_running ==
-              (running_var.defined() && running_var.numel() > 0), what,
-              ": running_mean and running_var go together");
-  if (has_running) {
-    bn_check_vec(running_mean, x, C, what, "running_mean");
-    bn_check_vec(running_var, x, C, what, "running_var");
-  }
-  if (res.has_value()) {
-    TORCH_CHECK(res->is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                res->scalar_type() == x.scalar_type() &&
-                res->device() == x.device() &&
-                res->sizes() == x.sizes(), what, ": bad residual");
-  }
+  const BnDims d = bn_check_input(x, what);
+  bn_check_vec(sums, x, 2 * (long)d.C + 1, what, "sums");
+  bn_check_channel_vecs(x, what, {{"gamma", gamma}, {"beta", beta}});
+  bn_check_running(running_mean, running_var, x, false, what);
+  if (res.has_value()) bn_check_like(*res, x, true, what, "bad residual");
   auto stream = at::hip::getCurrentHIPStream().stream();
   auto y = torch::empty_like(x);
-  auto fopts = x.options().dtype(at::kFloat);
-  auto mean = torch::empty({C}, fopts);
-  auto invstd = torch::empty({C}, fopts);
-  auto scale = torch::empty({C}, fopts);
-  auto bias = torch::empty({C}, fopts);
-  torch::Tensor mask;
-  if (relu)
-    mask = torch::empty({x.numel() / V}, x.options().dtype(at::kByte));
-  hipLaunchKernelGGL(bn_sync_stats_coef_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, sums.data_ptr<float>(),
-                     gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                     has_running ? running_mean.data_ptr<float>()
-                                 : nullptr,
-                     has_running ? running_var.data_ptr<float>()
-                                 : nullptr,
-                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                     scale.data_ptr<float>(), bias.data_ptr<float>(), C,
-                     (float)momentum, (float)eps);
+  torch::Tensor mask = torch::empty({relu ? x.numel() / d.V : 0},
+                                    x.options().dtype(at::kByte));
+  BnFwdOut o(x);
+  hipLaunchKernelGGL(bn_sync_stats_coef_kernel, bn_grid_channels(d.C),
+                     dim3(256), 0, stream, fptr(sums),
+                     o.args(gamma, beta, running_mean, running_var,
+                            momentum, eps), d.C);
   CHECK_HIP_BN(hipGetLastError());
-  if (x.scalar_type() == at::kBFloat16)
-    bn_launch_apply<__hip_bfloat16>(x, y, scale, bias, res, mask, relu, R,
-                                    C, stream);
-  else
-    bn_launch_apply<float>(x, y, scale, bias, res, mask, relu, R, C,
-                           stream);
-  if (!mask.defined())
-    mask = torch::empty({0}, x.options().dtype(at::kByte));
-  return {y, mean, invstd, mask};
+  bn_launch_apply(x, y, o, res, mask, relu, d, stream);
+  return {y, o.mean, o.invstd, mask};
 }
 
 // Returns bsums = fp32 [2C]: sum(dy_eff) (this rank's dbeta), then
@@ -1385,21 +1249,18 @@ std::vector<torch::Tensor> fused_bn_sync_apply(
 torch::Tensor fused_bn_sync_bwd_reduce(
     torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
     torch::Tensor mean, torch::Tensor invstd, bool relu) {
-  bn_check_bwd_args(dy, mask, x, mean, invstd, relu,
-                    "fused_bn_sync_bwd_reduce");
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
+  const BnDims d = bn_check_bwd_args(dy, mask, x, mean, invstd, relu,
+                                     "fused_bn_sync_bwd_reduce");
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  auto bsums = torch::empty({2 * (long)C}, mean.options());
-  torch::Tensor partial2 = x.scalar_type() == at::kBFloat16
-      ? bn_bwd_partial2<__hip_bfloat16>(dy, mask, x, mean, invstd, relu,
-                                        R, C, stream)
-      : bn_bwd_partial2<float>(dy, mask, x, mean, invstd, relu, R, C,
-                               stream);
-  hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, partial2.data_ptr<float>(),
-                     bsums.data_ptr<float>(), C, 0.f, false);
+  auto bsums = torch::empty({2 * (long)d.C}, bn_fopts(x));
+  torch::Tensor partial =
+      bn_bwd_partial(dy, mask, x, mean, invstd, relu, d, stream);
+  torch::Tensor partial2 =
+      bn_fold2(fptr(partial), (int)partial.size(1), x, stream);
+  hipLaunchKernelGGL(bn_sync_fold_kernel, bn_grid_channels(d.C),
+                     dim3(256), 0, stream, fptr(partial2), fptr(bsums),
+                     d.C, 0.f, false);
   CHECK_HIP_BN(hipGetLastError());
   return bsums;
 }
@@ -1411,33 +1272,22 @@ std::vector<torch::Tensor> fused_bn_sync_bwd_dx(
     torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma,
     torch::Tensor bsums, torch::Tensor count, bool relu, bool has_res) {
   const char* what = "fused_bn_sync_bwd_dx";
-  bn_check_bwd_args(dy, mask, x, mean, invstd, relu, what);
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
-  bn_check_vec(gamma, x, C, what, "gamma");
-  bn_check_vec(bsums, x, 2 * (long)C, what, "bsums");
+  const BnDims d = bn_check_bwd_args(dy, mask, x, mean, invstd, relu, what);
+  bn_check_channel_vecs(x, what, {{"gamma", gamma}});
+  bn_check_vec(bsums, x, 2 * (long)d.C, what, "bsums");
   bn_check_vec(count, x, 1, what, "count");
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   auto stream = at::hip::getCurrentHIPStream().stream();
   auto dx = torch::empty_like(x);
-  auto coefP = torch::empty({C}, mean.options());
-  auto coefQ = torch::empty({C}, mean.options());
-  auto coefS = torch::empty({C}, mean.options());
+  auto coef = torch::empty({3, d.C}, bn_fopts(x));
   c10::optional<torch::Tensor> dres;
   if (has_res) dres = torch::empty_like(x);
-  hipLaunchKernelGGL(bn_sync_bwd_coef_kernel, dim3((C + 255) / 256),
-                     dim3(256), 0, stream, bsums.data_ptr<float>(),
-                     count.data_ptr<float>(), gamma.data_ptr<float>(),
-                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                     coefP.data_ptr<float>(), coefQ.data_ptr<float>(),
-                     coefS.data_ptr<float>(), C);
+  hipLaunchKernelGGL(bn_sync_bwd_coef_kernel, bn_grid_channels(d.C),
+                     dim3(256), 0, stream, fptr(bsums), fptr(count),
+                     fptr(gamma), fptr(mean), fptr(invstd), fptr(coef),
+                     d.C);
   CHECK_HIP_BN(hipGetLastError());
-  if (x.scalar_type() == at::kBFloat16)
-    bn_launch_bwd_dx<__hip_bfloat16>(dy, mask, x, coefP, coefQ, coefS, dx,
-                                     dres, relu, R, C, stream);
-  else
-    bn_launch_bwd_dx<float>(dy, mask, x, coefP, coefQ, coefS, dx, dres,
-                            relu, R, C, stream);
+  bn_launch_bwd_dx(dy, mask, x, coef, dx, dres, relu, d, stream);
   std::vector<torch::Tensor> out = {dx};
   if (has_res) out.push_back(*dres);
   return out;
@@ -1451,62 +1301,68 @@ std::vector<torch::Tensor> fused_bn_relu_pool_fwd(
     torch::Tensor x, torch::Tensor gamma, torch::Tensor beta,
     torch::Tensor running_mean, torch::Tensor running_var,
     double momentum, double eps) {
-  bn_check_input(x, "fused_bn_relu_pool");
-  // the kernels index pixels and code words in 32 bits
-  TORCH_CHECK(x.numel() < (1L << 31), "fused_bn_relu_pool: input too large");
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
+  const char* what = "fused_bn_relu_pool_fwd";
+  const BnDims d = bn_check_pool_input(x, what);
+  bn_check_channel_vecs(x, what, {{"gamma", gamma}, {"beta", beta}});
+  bn_check_running(running_mean, running_var, x, false, what);
   const PoolGeom g = pool_geom(x);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  auto pooled = torch::empty({g.N, C, g.OH, g.OW}, x.options(),
+  auto pooled = torch::empty({g.N, d.C, g.OH, g.OW}, x.options(),
                              at::MemoryFormat::ChannelsLast);
-  auto code = torch::empty({(long)g.N * g.OH * g.OW * (C / V)},
-                           x.options().dtype(at::kInt));
-  auto fopts = gamma.options().dtype(at::kFloat);
-  auto mean = torch::empty({C}, fopts);
-  auto invstd = torch::empty({C}, fopts);
-  if (x.scalar_type() == at::kBFloat16)
-    bn_relu_pool_fwd_impl<__hip_bfloat16>(
-        x, pooled, code, gamma, beta, running_mean, running_var, mean,
-        invstd, momentum, eps, R, C, stream);
-  else
-    bn_relu_pool_fwd_impl<float>(
-        x, pooled, code, gamma, beta, running_mean, running_var, mean,
-        invstd, momentum, eps, R, C, stream);
-  return {pooled, mean, invstd, code};
+  const long nvec = (long)g.N * g.OH * g.OW * (d.C / d.V);
+  auto code = torch::empty({nvec}, x.options().dtype(at::kInt));
+  BnFwdOut o = bn_train_coefs(x, gamma, beta, running_mean, running_var,
+                              momentum, eps, d, stream);
+  BN_DISPATCH(x, hipLaunchKernelGGL(
+      (bn_relu_pool_apply_kernel<T>), dim3(bn_grid_elems(nvec)), dim3(kT),
+      0, stream, bn_ptr<const T>(x), bn_ptr<T>(pooled),
+      bn_ptr<unsigned int>(code), fptr(o.scale), fptr(o.bias),
+      (unsigned int)nvec, g.H, g.W, g.OH, g.OW, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  return {pooled, o.mean, o.invstd, code};
 }
 
 // Returns (dx, dgamma, dbeta).
 std::vector<torch::Tensor> fused_bn_relu_pool_bwd(
     torch::Tensor dpool, torch::Tensor code, torch::Tensor x,
     torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma) {
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
+  const char* what = "fused_bn_relu_pool_bwd";
+  const BnDims d = bn_check_pool_input(x, what);
   const PoolGeom g = pool_geom(x);
-  TORCH_CHECK(dpool.dim() == 4 && dpool.size(0) == g.N &&
-              dpool.size(1) == C && dpool.size(2) == g.OH &&
-              dpool.size(3) == g.OW &&
-              dpool.scalar_type() == x.scalar_type(),
-              "fused_bn_relu_pool_bwd: bad pooled gradient");
-  TORCH_CHECK(code.scalar_type() == at::kInt &&
-              code.numel() == (long)g.N * g.OH * g.OW * (C / V),
-              "fused_bn_relu_pool_bwd: bad code tensor");
+  TORCH_CHECK(dpool.defined() && dpool.dim() == 4 &&
+              dpool.size(0) == g.N && dpool.size(1) == d.C &&
+              dpool.size(2) == g.OH && dpool.size(3) == g.OW &&
+              dpool.scalar_type() == x.scalar_type() &&
+              dpool.device() == x.device(),
+              what, ": bad pooled gradient");
+  TORCH_CHECK(code.defined() && code.scalar_type() == at::kInt &&
+              code.device() == x.device() && code.is_contiguous() &&
+              code.numel() == (long)g.N * g.OH * g.OW * (d.C / d.V),
+              what, ": bad code tensor");
+  bn_check_channel_vecs(x, what, {{"mean", mean}, {"invstd", invstd},
+                                  {"gamma", gamma}});
   dpool = dpool.contiguous(at::MemoryFormat::ChannelsLast);
   auto stream = at::hip::getCurrentHIPStream().stream();
   auto dx = torch::empty_like(x);
-  auto fopts = gamma.options().dtype(at::kFloat);
-  auto dgamma = torch::empty({C}, fopts);
-  auto dbeta = torch::empty({C}, fopts);
-  if (x.scalar_type() == at::kBFloat16)
-    bn_relu_pool_bwd_impl<__hip_bfloat16>(dpool, code, x, mean, invstd,
-                                          gamma, dx, dgamma, dbeta, R, C,
-                                          stream);
-  else
-    bn_relu_pool_bwd_impl<float>(dpool, code, x, mean, invstd, gamma, dx,
-                                 dgamma, dbeta, R, C, stream);
-  return {dx, dgamma, dbeta};
+  const int lines = g.N * g.H;
+  const int nb = bn_stage1_blocks(d);
+  auto partial = torch::empty({2, nb, d.C}, bn_fopts(x));
+  BN_DISPATCH(x, hipLaunchKernelGGL(
+      (bn_pool_bwd_reduce_kernel<T>), dim3(nb), dim3(kT), 0, stream,
+      bn_ptr<const T>(dpool), bn_ptr<const unsigned int>(code),
+      bn_ptr<const T>(x), fptr(mean), fptr(invstd), fptr(partial), d.R,
+      g.H, g.W, g.OH, g.OW, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  BnBwdOut o = bn_bwd_fold_coefs(fptr(partial), nb, x, gamma, mean, invstd,
+                                 d, stream);
+  const float* cf = fptr(o.coef);
+  BN_DISPATCH(x, hipLaunchKernelGGL(
+      (bn_pool_bwd_dx_kernel<T>), dim3(std::min(lines, 16384)), dim3(kT),
+      0, stream, bn_ptr<const T>(dpool), bn_ptr<const unsigned int>(code),
+      bn_ptr<const T>(x), cf, cf + d.C, cf + 2 * d.C, bn_ptr<T>(dx),
+      lines, g.H, g.W, g.OH, g.OW, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  return {dx, o.dgamma, o.dbeta};
 }
 
 // y = relu(BN3(x3) + BNd(xd)), both BNs in training mode.
@@ -1518,34 +1374,29 @@ std::vector<torch::Tensor> fused_bn_dual_fwd(
     torch::Tensor betad, torch::Tensor running_meand,
     torch::Tensor running_vard, double momentum3, double momentumd,
     double eps3, double epsd) {
-  bn_check_input(x3, "fused_bn_dual");
-  bn_check_input(xd, "fused_bn_dual");
-  TORCH_CHECK(xd.sizes() == x3.sizes() &&
-              xd.scalar_type() == x3.scalar_type(),
-              "fused_bn_dual: the two inputs must match");
-  const int C = (int)x3.size(1);
-  const long R = x3.numel() / C;
-  const int V = x3.scalar_type() == at::kBFloat16 ? 8 : 4;
+  const char* what = "fused_bn_dual_fwd";
+  const BnDims d = bn_check_input(x3, what);
+  bn_check_like(xd, x3, true, what, "the two inputs must match");
+  bn_check_channel_vecs(x3, what, {{"gamma3", gamma3}, {"beta3", beta3},
+                                   {"gammad", gammad}, {"betad", betad}});
+  bn_check_running(running_mean3, running_var3, x3, false, what);
+  bn_check_running(running_meand, running_vard, x3, false, what);
   auto stream = at::hip::getCurrentHIPStream().stream();
   auto y = torch::empty_like(x3);
-  auto mask = torch::empty({x3.numel() / V},
+  auto mask = torch::empty({x3.numel() / d.V},
                            x3.options().dtype(at::kByte));
-  auto fopts = gamma3.options().dtype(at::kFloat);
-  auto mean3 = torch::empty({C}, fopts);
-  auto invstd3 = torch::empty({C}, fopts);
-  auto meand = torch::empty({C}, fopts);
-  auto invstdd = torch::empty({C}, fopts);
-  if (x3.scalar_type() == at::kBFloat16)
-    bn_dual_fwd_impl<__hip_bfloat16>(
-        x3, xd, y, mask, gamma3, beta3, running_mean3, running_var3,
-        gammad, betad, running_meand, running_vard, mean3, invstd3,
-        meand, invstdd, momentum3, momentumd, eps3, epsd, R, C, stream);
-  else
-    bn_dual_fwd_impl<float>(
-        x3, xd, y, mask, gamma3, beta3, running_mean3, running_var3,
-        gammad, betad, running_meand, running_vard, mean3, invstd3,
-        meand, invstdd, momentum3, momentumd, eps3, epsd, R, C, stream);
-  return {y, mean3, invstd3, meand, invstdd, mask};
+  BnFwdOut od = bn_train_coefs(xd, gammad, betad, running_meand,
+                               running_vard, momentumd, epsd, d, stream);
+  BnFwdOut o3 = bn_train_coefs(x3, gamma3, beta3, running_mean3,
+                               running_var3, momentum3, eps3, d, stream);
+  const long total = d.R * (long)d.C;
+  BN_DISPATCH(x3, hipLaunchKernelGGL(
+      (bn_dual_apply_kernel<T>), dim3(bn_grid_elems(total / d.V)),
+      dim3(kT), 0, stream, bn_ptr<const T>(x3), bn_ptr<const T>(xd),
+      bn_ptr<T>(y), fptr(o3.scale), fptr(o3.bias), fptr(od.scale),
+      fptr(od.bias), mask.data_ptr<unsigned char>(), total, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  return {y, o3.mean, o3.invstd, od.mean, od.invstd, mask};
 }
 
 // Returns (dx3, dxd, dgamma3, dbeta3, dgammad, dbetad).
@@ -1554,103 +1405,37 @@ std::vector<torch::Tensor> fused_bn_dual_bwd(
     torch::Tensor xd, torch::Tensor mean3, torch::Tensor invstd3,
     torch::Tensor gamma3, torch::Tensor meand, torch::Tensor invstdd,
     torch::Tensor gammad) {
-  const int C = (int)x3.size(1);
-  const long R = x3.numel() / C;
-  const int V = x3.scalar_type() == at::kBFloat16 ? 8 : 4;
-  TORCH_CHECK(dy.sizes() == x3.sizes() && xd.sizes() == x3.sizes() &&
-              dy.scalar_type() == x3.scalar_type(),
-              "fused_bn_dual_bwd: bad gradient");
-  TORCH_CHECK(mask.numel() == x3.numel() / V,
-              "fused_bn_dual_bwd: needs the fwd mask");
+  const char* what = "fused_bn_dual_bwd";
+  const BnDims d =
+      bn_check_bwd_args(dy, mask, x3, mean3, invstd3, true, what);
+  bn_check_like(xd, x3, true, what, "the two inputs must match");
+  bn_check_channel_vecs(x3, what, {{"gamma3", gamma3}, {"meand", meand},
+                                   {"invstdd", invstdd},
+                                   {"gammad", gammad}});
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  auto fopts = gamma3.options().dtype(at::kFloat);
-  std::vector<torch::Tensor> out = {
-      torch::empty_like(x3), torch::empty_like(xd),
-      torch::empty({C}, fopts), torch::empty({C}, fopts),
-      torch::empty({C}, fopts), torch::empty({C}, fopts)};
-  if (x3.scalar_type() == at::kBFloat16)
-    bn_dual_bwd_impl<__hip_bfloat16>(dy, mask, x3, xd, mean3, invstd3,
-                                     gamma3, meand, invstdd, gammad, out,
-                                     R, C, stream);
-  else
-    bn_dual_bwd_impl<float>(dy, mask, x3, xd, mean3, invstd3, gamma3,
-                            meand, invstdd, gammad, out, R, C, stream);
-  return out;
-}
-
-// x: [N, C, H, W] channels_last (viewed as [R, C]); gamma/beta fp32.
-// Returns (y, save_mean, save_invstd).
-std::vector<torch::Tensor> fused_bn_fwd(
-    torch::Tensor x, torch::Tensor gamma, torch::Tensor beta,
-    torch::Tensor running_mean, torch::Tensor running_var,
-    c10::optional<torch::Tensor> res, bool relu, bool training,
-    double momentum, double eps) {
-  TORCH_CHECK(x.dim() == 4, "fused_bn: 4-D input expected");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "fused_bn: channels_last input required");
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
-  const int V = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  TORCH_CHECK(C % V == 0 && C / V <= kT,
-              "fused_bn: C=", C, " unsupported for vec", V);
-  if (res.has_value()) {
-    TORCH_CHECK(res->is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                res->scalar_type() == x.scalar_type() &&
-                res->sizes() == x.sizes(), "fused_bn: bad residual");
-  }
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  auto y = torch::empty_like(x);  // keeps channels_last layout
-  auto fopts = gamma.options().dtype(at::kFloat);
-  auto mean = torch::empty({C}, fopts);
-  auto invstd = torch::empty({C}, fopts);
-  // ReLU bitmask (1 byte per V elems) replaces re-reading y in
-  // backward: ~25% less bwd traffic
-  torch::Tensor mask;
-  if (relu && training)
-    mask = torch::empty({x.numel() / V},
-                        x.options().dtype(at::kByte));
-  if (x.scalar_type() == at::kBFloat16)
-    bn_fwd_impl<__hip_bfloat16>(x, y, gamma, beta, running_mean,
-                                running_var, mean, invstd, res, mask,
-                                relu, training, momentum, eps, R, C,
-                                stream);
-  else if (x.scalar_type() == at::kFloat)
-    bn_fwd_impl<float>(x, y, gamma, beta, running_mean, running_var,
-                       mean, invstd, res, mask, relu, training,
-                       momentum, eps, R, C, stream);
-  else
-    TORCH_CHECK(false, "fused_bn: dtype must be bf16 or f32");
-  if (!mask.defined())
-    mask = torch::empty({0}, x.options().dtype(at::kByte));
-  return {y, mean, invstd, mask};
-}
-
-// Returns (dx, dgamma, dbeta[, dres]). mask: ReLU bitmask from fwd
-// (empty tensor when relu=false).
-std::vector<torch::Tensor> fused_bn_bwd(
-    torch::Tensor dy, torch::Tensor mask, torch::Tensor x,
-    torch::Tensor mean, torch::Tensor invstd, torch::Tensor gamma,
-    bool relu, bool has_res) {
-  const int C = (int)x.size(1);
-  const long R = x.numel() / C;
-  TORCH_CHECK(!relu || mask.numel() > 0,
-              "fused_bn_bwd: relu path needs the fwd mask");
-  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  auto dx = torch::empty_like(x);
-  auto fopts = gamma.options().dtype(at::kFloat);
-  auto dgamma = torch::empty({C}, fopts);
-  auto dbeta = torch::empty({C}, fopts);
-  c10::optional<torch::Tensor> dres;
-  if (has_res) dres = torch::empty_like(x);
-  if (x.scalar_type() == at::kBFloat16)
-    bn_bwd_impl<__hip_bfloat16>(dy, mask, x, mean, invstd, gamma, dx,
-                                dgamma, dbeta, dres, relu, R, C, stream);
-  else
-    bn_bwd_impl<float>(dy, mask, x, mean, invstd, gamma, dx, dgamma,
-                       dbeta, dres, relu, R, C, stream);
-  std::vector<torch::Tensor> out = {dx, dgamma, dbeta};
-  if (has_res) out.push_back(*dres);
-  return out;
+  auto dx3 = torch::empty_like(x3);
+  auto dxd = torch::empty_like(xd);
+  const int nb = bn_stage1_blocks(d);
+  auto partial = torch::empty({4, nb, d.C}, bn_fopts(x3));
+  const unsigned char* mp = mask.data_ptr<unsigned char>();
+  BN_DISPATCH(x3, hipLaunchKernelGGL(
+      (bn_dual_bwd_reduce_kernel<T>), dim3(nb), dim3(kT), 0, stream,
+      bn_ptr<const T>(dy), mp, bn_ptr<const T>(x3), bn_ptr<const T>(xd),
+      fptr(mean3), fptr(invstd3), fptr(meand), fptr(invstdd),
+      fptr(partial), d.R, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  const float* pp = fptr(partial);
+  BnBwdOut o3 = bn_bwd_fold_coefs(pp, nb, x3, gamma3, mean3, invstd3, d,
+                                  stream);
+  BnBwdOut od = bn_bwd_fold_coefs(pp + 2 * (long)nb * d.C, nb, x3, gammad,
+                                  meand, invstdd, d, stream);
+  const long total = d.R * (long)d.C;
+  BN_DISPATCH(x3, hipLaunchKernelGGL(
+      (bn_dual_bwd_dx_kernel<T>), dim3(bn_grid_elems(total / d.V)),
+      dim3(kT), 0, stream, bn_ptr<const T>(dy), mp, bn_ptr<const T>(x3),
+      bn_ptr<const T>(xd), fptr(o3.coef), fptr(od.coef), bn_ptr<T>(dx3),
+      bn_ptr<T>(dxd), total, d.C));
+  CHECK_HIP_BN(hipGetLastError());
+  return {dx3, dxd, o3.dgamma, o3.dbeta, od.dgamma, od.dbeta};
 }

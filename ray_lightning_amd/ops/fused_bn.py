@@ -28,28 +28,34 @@ from . import _load_ext
 
 
 def _fusable(x: torch.Tensor, c: int) -> bool:
-    if not x.is_cuda or x.dim() != 4:
+    """What the extension's operand check admits as the activation."""
+    if not x.is_cuda or x.dim() != 4 or x.numel() == 0:
         return False
     if x.dtype not in (torch.bfloat16, torch.float32):
         return False
     v = 8 if x.dtype == torch.bfloat16 else 4
-    if c % v or c // v > 256:
+    tpr = c // v
+    # a power-of-two C/V: only then do the stage-1 reduction trees cover
+    # every row of a block
+    if c % v or tpr > 256 or tpr & (tpr - 1):
         return False
     return x.is_contiguous(memory_format=torch.channels_last) and \
         _load_ext() is not None
+
+
+def _or_empty(t: Optional[torch.Tensor]) -> torch.Tensor:
+    """The extension takes an empty tensor for "no running stats"."""
+    return t if t is not None else torch.Tensor()
 
 
 class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean,
                 running_var, training, momentum, eps, relu):
-        ext = _load_ext()
-        res_opt = residual
-        y, mean, invstd, mask = ext.fused_bn_fwd(
-            x, weight, bias,
-            running_mean if running_mean is not None else torch.Tensor(),
-            running_var if running_var is not None else torch.Tensor(),
-            res_opt, relu, training, momentum, eps)
+        y, mean, invstd, mask = _load_ext().fused_bn_fwd(
+            x, weight, bias, _or_empty(running_mean),
+            _or_empty(running_var), residual, relu, training, momentum,
+            eps)
         ctx.relu = relu
         ctx.has_res = residual is not None
         # the ReLU bitmask (1 byte / 8 elems) replaces saving+re-reading
@@ -79,10 +85,8 @@ class _FusedBNReluPoolFunction(torch.autograd.Function):
                 momentum, eps):
         ext = _load_ext()
         pooled, mean, invstd, code = ext.fused_bn_relu_pool_fwd(
-            x, weight, bias,
-            running_mean if running_mean is not None else torch.Tensor(),
-            running_var if running_var is not None else torch.Tensor(),
-            momentum, eps)
+            x, weight, bias, _or_empty(running_mean),
+            _or_empty(running_var), momentum, eps)
         ctx.save_for_backward(x, code, mean, invstd, weight)
         return pooled
 
@@ -101,12 +105,11 @@ class _FusedDualBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x3, xd, w3, b3, rm3, rv3, wd, bd, rmd, rvd,
                 momentum3, momentumd, eps3, epsd):
-        def _t(t):
-            return t if t is not None else torch.Tensor()
         y, mean3, invstd3, meand, invstdd, mask = \
             _load_ext().fused_bn_dual_fwd(
-                x3, xd, w3, b3, _t(rm3), _t(rv3), wd, bd, _t(rmd),
-                _t(rvd), momentum3, momentumd, eps3, epsd)
+                x3, xd, w3, b3, _or_empty(rm3), _or_empty(rv3), wd, bd,
+                _or_empty(rmd), _or_empty(rvd), momentum3, momentumd,
+                eps3, epsd)
         ctx.save_for_backward(x3, xd, mask, mean3, invstd3, w3, meand,
                               invstdd, wd)
         return y
@@ -249,14 +252,6 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
 #   sums  = [sum(x) | sum(x^2) | row count]     fp32 [2C+1]
 #   bsums = [sum(dy_eff) | sum(dy_eff * xhat)]  fp32 [2C]
 # ---------------------------------------------------------------------
-def _sync_kernel_shape(x: torch.Tensor, c: int) -> bool:
-    """The sync entry points additionally want C/V to be a power of two:
-    only then do the stage-1 reduction trees cover every row of a
-    block."""
-    tpr = c // (8 if x.dtype == torch.bfloat16 else 4)
-    return tpr > 0 and tpr & (tpr - 1) == 0
-
-
 def _per_channel(v: torch.Tensor) -> torch.Tensor:
     return v.view(1, -1, 1, 1)
 
@@ -339,12 +334,8 @@ class _FusedSyncBNFunction(torch.autograd.Function):
         comm.all_reduce_(sums, op="sum", async_op=False)
         if use_ext:
             y, mean, invstd, mask = ext.fused_bn_sync_apply(
-                x, sums, weight, bias,
-                running_mean if running_mean is not None
-                else torch.Tensor(),
-                running_var if running_var is not None
-                else torch.Tensor(),
-                residual, relu, momentum, eps)
+                x, sums, weight, bias, _or_empty(running_mean),
+                _or_empty(running_var), residual, relu, momentum, eps)
         else:
             y, mean, invstd, mask = _twin_apply(
                 x, sums, weight, bias, running_mean, running_var,
@@ -426,7 +417,6 @@ class FusedSyncBatchNorm2d(FusedBatchNorm2d):
             return super().forward(x, residual)
         self._check_input_dim(x)
         use_ext = self._kernel_ready(x) and \
-            _sync_kernel_shape(x, self.num_features) and \
             self.bias is not None and \
             (residual is None or (residual.dtype == x.dtype and
                                   residual.shape == x.shape)) and \

@@ -193,7 +193,7 @@ def test_gate_non_power_of_two_takes_the_twin(monkeypatch, c, engaged):
         bn.bias.copy_(b)
     x = xs[0].cuda().requires_grad_()
     res = ress[0].cuda().requires_grad_()
-    assert bn._kernel_ready(x)  # the existing gate admits both widths
+    assert bn._kernel_ready(x) == engaged
     y = bn(x, res)
     y.backward(dys[0].cuda())
     torch.cuda.synchronize()
