@@ -114,9 +114,17 @@ class GPT2LM(LightningModule):
                  bf16_weights: bool = True, embd_pdrop: float = 0.0,
                  resid_pdrop: float = 0.0, attn_pdrop: float = 0.0,
                  ignore_index: int = -100, label_smoothing: float = 0.0,
-                 z_loss: float = 0.0, doc_eos_id: Optional[int] = None):
+                 z_loss: float = 0.0, doc_eos_id: Optional[int] = None,
+                 gen_max_new_tokens: int = 32, gen_temperature: float = 0.0,
+                 gen_top_k: Optional[int] = None,
+                 gen_eos_id: Optional[int] = None):
         super().__init__()
         self.save_hyperparameters()
+        # predict_step: how GPT2.generate continues a batch of prompts
+        self.gen_max_new_tokens = gen_max_new_tokens
+        self.gen_temperature = gen_temperature
+        self.gen_top_k = gen_top_k
+        self.gen_eos_id = gen_eos_id
         # packed rows: when set, training_step derives document ids from
         # this EOS token and attention / positions stay within documents
         self.doc_eos_id = doc_eos_id
@@ -155,6 +163,22 @@ class GPT2LM(LightningModule):
             _, loss = self(x, y)
         self.log("train_loss", loss)
         return loss
+
+    def predict_step(self, batch, batch_idx):
+        """Continue a batch of prompts: ``batch`` is ``idx`` [B, P], or
+        ``(idx, prompt_lens)`` for right-padded prompts of different
+        lengths. Returns ``GPT2.generate``'s tokens
+        [B, P + gen_max_new_tokens]."""
+        prompt_lens = None
+        if isinstance(batch, (tuple, list)):
+            idx, prompt_lens = batch
+            prompt_lens = torch.as_tensor(prompt_lens).cpu()
+        else:
+            idx = batch
+        return self.model.generate(
+            idx, self.gen_max_new_tokens, prompt_lens=prompt_lens,
+            temperature=self.gen_temperature, top_k=self.gen_top_k,
+            eos_token_id=self.gen_eos_id)
 
     def configure_optimizers(self):
         decay, no_decay = [], []

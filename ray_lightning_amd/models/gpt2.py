@@ -18,6 +18,12 @@ and positions within each document (``document_ids`` derives the ids
 from an EOS token; ops/flash_attn.py has the kernels). Masking the
 target that follows an EOS stays with the data pipeline, through
 ``ignore_index``.
+
+Generation: ``GPT2.generate`` samples from the model with a KV cache
+(ops/decode_attn.py): one prefill forward over the prompts on the flash
+kernels, then one token per row per step through the split-KV decode
+attention kernel, which also appends to the cache. ``forward(idx,
+cache=...)`` is the same machinery one call at a time.
 """
 from __future__ import annotations
 
@@ -78,14 +84,28 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x, doc_ids=None):
+    def forward(self, x, doc_ids=None, cache=None):
+        """``cache`` is this layer's ``(k_cache, v_cache, kv)`` of a
+        ``KVCache`` ``kv``. Before the prefill the call attends as it
+        does without a cache and copies its k and v into the caches at
+        ``[:, :, :T]``; after it, ``x`` is one new token per row and
+        attention is ``decode_attention`` over the cache."""
         B, T, C = x.shape
         qkv = self.c_attn(x)
+        if cache is not None and cache[2].prefilled:
+            from ..ops.decode_attn import decode_attention
+            k_cache, v_cache, kv = cache
+            y = decode_attention(qkv.view(B, 3 * C), k_cache, v_cache,
+                                 kv.pos, kv.max_pos, self.n_head)
+            return self.c_proj(y.view(B, 1, C))
         q, k, v = qkv.split(C, dim=2)
         hs = C // self.n_head
         q = q.view(B, T, self.n_head, hs).transpose(1, 2)
         k = k.view(B, T, self.n_head, hs).transpose(1, 2)
         v = v.view(B, T, self.n_head, hs).transpose(1, 2)
+        if cache is not None:
+            cache[0][:, :, :T].copy_(k)
+            cache[1][:, :, :T].copy_(v)
         # hand-written MFMA flash kernels when the shape qualifies
         # (causal bf16 hs=64), attention dropout and document masking
         # (doc_ids: ids [B, T] or the doc_bounds pair) included; SDPA
@@ -163,13 +183,55 @@ class GPT2(nn.Module):
 
     def forward(self, idx: torch.Tensor,
                 targets: Optional[torch.Tensor] = None,
-                doc_ids: Optional[torch.Tensor] = None):
+                doc_ids: Optional[torch.Tensor] = None,
+                cache=None):
         """``doc_ids`` (integer [B, T], e.g. from ``document_ids``) marks
         the documents of packed rows: attention stays within a document
         and positions restart at each document's first token, so a
-        packed document computes what it would compute alone."""
+        packed document computes what it would compute alone.
+
+        ``cache`` (a ``KVCache``, inference only): the first call with
+        it is the prefill, an ordinary forward over ``idx`` [B, T] that
+        also fills the cache and sets every row's length to ``T``; each
+        later call takes one new token per row, ``idx`` [B, 1], at the
+        rows' own positions ``cache.pos`` and returns its logits
+        [B, 1, V]."""
+        x = self._hidden(idx, doc_ids, cache)
+        if targets is not None:
+            # chunked LM-head + CE: never materializes the [B*T, V]
+            # logits (ops/chunked_ce.py); identical numerics to
+            # F.cross_entropy(logits.float(), t, ignore_index=,
+            # label_smoothing=) + z_loss * mean(logsumexp^2)
+            from ..ops.chunked_ce import chunked_cross_entropy
+            loss = chunked_cross_entropy(
+                x.reshape(-1, x.size(-1)), self.lm_head.weight,
+                targets.reshape(-1),
+                ignore_index=self.cfg.ignore_index,
+                label_smoothing=self.cfg.label_smoothing,
+                z_loss=self.cfg.z_loss)
+            return None, loss
+        return self.lm_head(x), None
+
+    def _hidden(self, idx, doc_ids=None, cache=None):
+        """``ln_f`` of the last block's output, [B, T, C]: forward
+        without the LM head."""
         B, T = idx.shape
-        pos = torch.arange(T, device=idx.device)
+        decode = cache is not None and cache.prefilled
+        if cache is not None:
+            if doc_ids is not None:
+                raise ValueError("doc_ids and cache do not combine")
+            if decode and T != 1:
+                raise ValueError(
+                    f"a decode step takes one token per row, got T = {T}")
+            # a decode step writes slot max_pos at the furthest, the
+            # prefill slots 0 .. T-1
+            if (cache.max_pos + 1 if decode else T) > cache.Tmax:
+                raise ValueError(
+                    f"the cache holds {cache.Tmax} positions per row")
+        if decode:
+            pos = cache.pos.to(torch.int64)[:, None]
+        else:
+            pos = torch.arange(T, device=idx.device)
         bounds = None
         if doc_ids is not None:
             # once per batch; every layer gets the pair
@@ -193,28 +255,150 @@ class GPT2(nn.Module):
         else:
             h = self.h[0].ln_1(x)
         for i, block in enumerate(self.h):
-            attn_out = block.attn(h, bounds)
+            if cache is None:
+                attn_out = block.attn(h, bounds)
+            else:
+                attn_out = block.attn(
+                    h, None, (cache.k[i], cache.v[i], cache))
             x, h = block.ln_2(attn_out, residual=x, dropout_p=pr)
             mlp_out = block.mlp(h)
             next_ln = (self.h[i + 1].ln_1 if i + 1 < len(self.h)
                        else self.ln_f)
             x, h = next_ln(mlp_out, residual=x, dropout_p=pr)
-        x = h  # = ln_f(x)
-        if targets is not None:
-            # chunked LM-head + CE: never materializes the [B*T, V]
-            # logits (ops/chunked_ce.py); identical numerics to
-            # F.cross_entropy(logits.float(), t, ignore_index=,
-            # label_smoothing=) + z_loss * mean(logsumexp^2)
-            from ..ops.chunked_ce import chunked_cross_entropy
-            loss = chunked_cross_entropy(
-                x.reshape(-1, x.size(-1)), self.lm_head.weight,
-                targets.reshape(-1),
-                ignore_index=self.cfg.ignore_index,
-                label_smoothing=self.cfg.label_smoothing,
-                z_loss=self.cfg.z_loss)
-            return None, loss
-        return self.lm_head(x), None
+        if decode:
+            cache.advance()
+        elif cache is not None:
+            cache.set_lengths(
+                torch.full((B,), T, dtype=torch.int32, device=idx.device),
+                T)
+        return h  # = ln_f(x)
 
+    @staticmethod
+    def _sample(logits, temperature, top_k, generator):
+        if temperature == 0:
+            return logits.argmax(dim=-1)
+        logits = logits / temperature
+        if top_k is not None:
+            kth = logits.topk(min(top_k, logits.size(-1)), dim=-1).values
+            logits = logits.masked_fill(logits < kth[:, -1:], -math.inf)
+        probs = torch.softmax(logits, dim=-1)
+        return torch.multinomial(probs, 1, generator=generator)[:, 0]
+
+    @torch.no_grad()
+    def generate(self, idx: torch.Tensor, max_new_tokens: int, *,
+                 prompt_lens=None, temperature: float = 1.0,
+                 top_k: Optional[int] = None,
+                 eos_token_id: Optional[int] = None,
+                 pad_token_id: int = 0,
+                 generator: Optional[torch.Generator] = None,
+                 return_logits: bool = False):
+        """Sample ``max_new_tokens`` tokens per row after the prompts.
+
+        ``idx`` [B, P] holds the prompts, right-padded; ``prompt_lens``
+        (list or CPU tensor, default all ``P``) their true lengths.
+        Returns tokens [B, P + max_new_tokens]: row ``b`` is its prompt,
+        its new tokens from position ``prompt_lens[b]`` on, then
+        ``pad_token_id``. Raises ``ValueError`` for a length outside
+        ``[1, P]`` or when ``max(prompt_lens) + max_new_tokens`` exceeds
+        ``n_positions``.
+
+        ``temperature == 0`` is greedy; otherwise the logits are divided
+        by ``temperature``, cut to the ``top_k`` largest when given, and
+        sampled with ``torch.multinomial`` on ``generator``. A row that
+        has emitted ``eos_token_id`` emits ``pad_token_id`` from then on.
+
+        One prefill forward over the prompts (padded up to a multiple of
+        64 positions so the flash kernels take it; the LM head runs on
+        the ``B`` rows at ``prompt_lens - 1`` only) fills a KV cache;
+        every later token costs one decode step over [B, 1]. Nothing is
+        read back from the device per token: whether every row has
+        finished is looked at once in 16 steps.
+
+        ``return_logits=True`` also returns the fp32 logits every step
+        sampled from, [B, max_new_tokens, V] (zero for steps after an
+        early stop). That tensor is for tests and small vocabularies: at
+        GPT-2's vocabulary it is 200 KB per row and step.
+
+        Runs without gradients, in eval mode; the module's mode is put
+        back afterwards."""
+        from ..ops.decode_attn import KVCache, decode_attn_chunk
+        cfg = self.cfg
+        if idx.dim() != 2:
+            raise ValueError("idx must be [B, P]")
+        B, P = idx.shape
+        if max_new_tokens < 0:
+            raise ValueError("max_new_tokens must be >= 0")
+        if prompt_lens is None:
+            lens = [P] * B
+        else:
+            lens = [int(n) for n in (prompt_lens.tolist() if isinstance(
+                prompt_lens, torch.Tensor) else prompt_lens)]
+        if len(lens) != B or not all(1 <= n <= P for n in lens):
+            raise ValueError(
+                f"prompt_lens must hold {B} lengths in [1, {P}], got {lens}")
+        max_len = max(lens)
+        if max_len + max_new_tokens > cfg.n_positions:
+            raise ValueError(
+                f"max(prompt_lens) + max_new_tokens = "
+                f"{max_len + max_new_tokens} exceeds n_positions = "
+                f"{cfg.n_positions}")
+        dev = idx.device
+        lens_dev = torch.tensor(lens, dtype=torch.int64, device=dev)
+        out = torch.full((B, P + max_new_tokens), pad_token_id,
+                         dtype=idx.dtype, device=dev)
+        in_prompt = torch.arange(P, device=dev)[None, :] < lens_dev[:, None]
+        out[:, :P] = torch.where(in_prompt, idx, out[:, :P])
+        V = cfg.vocab_size
+        all_logits = torch.zeros(B, max_new_tokens, V, dtype=torch.float32,
+                                 device=dev) if return_logits else None
+        if max_new_tokens == 0:
+            return (out, all_logits) if return_logits else out
+
+        was_training = self.training
+        self.eval()
+        try:
+            # prefill: padding sits after the real tokens, so under
+            # causal attention it cannot reach them
+            P_pad = min(-(-P // 64) * 64, max(cfg.n_positions, P))
+            prompt = out.new_full((B, P_pad), pad_token_id)
+            prompt[:, :P] = out[:, :P]
+            cache = None
+            if max_new_tokens > 1:
+                chunk = decode_attn_chunk()
+                Tmax = -(-(max_len + max_new_tokens) // chunk) * chunk
+                Tmax = max(min(Tmax, cfg.n_positions), P_pad)
+                p0 = self.wte.weight
+                cache = KVCache(cfg.n_layer, B, cfg.n_head, Tmax,
+                                cfg.n_embd // cfg.n_head, p0.dtype, dev)
+            h = self._hidden(prompt, None, cache)
+            if cache is not None:
+                # pad positions in the cache are overwritten as the row
+                # grows, and never attended before that
+                cache.set_lengths(lens_dev.to(torch.int32), max_len)
+            h = h[torch.arange(B, device=dev), lens_dev - 1]
+            logits = self.lm_head(h).float()
+
+            finished = torch.zeros(B, dtype=torch.bool, device=dev)
+            for step in range(max_new_tokens):
+                if return_logits:
+                    all_logits[:, step] = logits
+                tok = self._sample(logits, temperature, top_k, generator)
+                if eos_token_id is not None:
+                    tok = torch.where(finished, tok.new_tensor(pad_token_id),
+                                      tok)
+                    finished = finished | (tok == eos_token_id)
+                out.scatter_(1, (lens_dev + step)[:, None],
+                             tok[:, None].to(out.dtype))
+                if step + 1 == max_new_tokens:
+                    break
+                if (eos_token_id is not None and step % 16 == 15
+                        and bool(finished.all())):
+                    break
+                h = self._hidden(tok[:, None], None, cache)
+                logits = self.lm_head(h[:, 0]).float()
+        finally:
+            self.train(was_training)
+        return (out, all_logits) if return_logits else out
 
 def document_ids(idx: torch.Tensor, eos_token_id: int) -> torch.Tensor:
     """Document ids [B, T] of a packed token stream: the number of EOS

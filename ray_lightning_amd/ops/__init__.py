@@ -16,6 +16,8 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
   multiplier inside the fused optimizer kernels
 - softmax cross-entropy forward/backward over logits rows with
   ignore_index, label smoothing and z-loss (``chunked_ce.py``)
+- single-token attention over a KV cache, split along the KV range, with
+  the cache append in the same launch (``decode_attn.py``)
 """
 from __future__ import annotations
 

@@ -35,6 +35,7 @@ def build(verbose: bool = False) -> None:
                       os.path.join(_CSRC, "fused_ce.hip"),
                       os.path.join(_CSRC, "flash_attn.hip"),
                       os.path.join(_CSRC, "conv1x1_bwd.hip"),
+                      os.path.join(_CSRC, "decode_attn.hip"),
                       os.path.join(_CSRC, "mfma_probe.hip")], []),
         ("_rccl_comm", [os.path.join(_CSRC, "rccl_comm.hip")],
          ["-L/opt/rocm/lib", "-lrccl"]),

@@ -1060,6 +1060,17 @@ torch::Tensor conv1x1_bwd_data(torch::Tensor dy, torch::Tensor w,
                                c10::optional<torch::Tensor> skip);
 bool conv1x1_bwd_data_supported(long cout, long cin);
 long conv1x1_bwd_data_row_tile(long cout, long cin);
+// single-token attention over a KV cache, split along the KV range, with
+// the append of the new k/v row — defined in decode_attn.hip
+torch::Tensor decode_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
+                              torch::Tensor v_cache, torch::Tensor pos,
+                              int64_t max_pos, double scale);
+torch::Tensor decode_attn_fwd_at_chunk(torch::Tensor qkv,
+                                       torch::Tensor k_cache,
+                                       torch::Tensor v_cache,
+                                       torch::Tensor pos, int64_t max_pos,
+                                       double scale, int64_t chunk);
+long decode_attn_chunk();
 // layout / instruction-semantics probes — defined in mfma_probe.hip
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor permlane_swap_probe();
@@ -1237,6 +1248,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "whether conv1x1_bwd_data has a kernel for (Cout, Cin)");
   m.def("conv1x1_bwd_data_row_tile", &conv1x1_bwd_data_row_tile,
         "rows per workgroup tile of conv1x1_bwd_data for (Cout, Cin)");
+  m.def("decode_attn_fwd", &decode_attn_fwd,
+        "single-token attention over a KV cache (split-KV) + append",
+        pybind11::arg("qkv"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("pos"),
+        pybind11::arg("max_pos"), pybind11::arg("scale"));
+  m.def("decode_attn_fwd_at_chunk", &decode_attn_fwd_at_chunk,
+        "decode_attn_fwd at a chunk size of 64, 128 or 256 (measurement)");
+  m.def("decode_attn_chunk", &decode_attn_chunk,
+        "KV positions per workgroup of decode_attn_fwd");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");
