@@ -98,24 +98,31 @@ class CausalSelfAttention(nn.Module):
             y = decode_attention(qkv.view(B, 3 * C), k_cache, v_cache,
                                  kv.pos, kv.max_pos, self.n_head)
             return self.c_proj(y.view(B, 1, C))
-        q, k, v = qkv.split(C, dim=2)
-        hs = C // self.n_head
-        q = q.view(B, T, self.n_head, hs).transpose(1, 2)
-        k = k.view(B, T, self.n_head, hs).transpose(1, 2)
-        v = v.view(B, T, self.n_head, hs).transpose(1, 2)
         if cache is not None:
-            cache[0][:, :, :T].copy_(k)
-            cache[1][:, :, :T].copy_(v)
+            # the prefill's cache fill, from the strided k and v views
+            hs = C // self.n_head
+            _, k, v = qkv.split(C, dim=2)
+            cache[0][:, :, :T].copy_(
+                k.view(B, T, self.n_head, hs).transpose(1, 2))
+            cache[1][:, :, :T].copy_(
+                v.view(B, T, self.n_head, hs).transpose(1, 2))
         # hand-written MFMA flash kernels when the shape qualifies
-        # (causal bf16 hs=64), attention dropout and document masking
-        # (doc_ids: ids [B, T] or the doc_bounds pair) included; SDPA
-        # (AOTriton) otherwise
-        from ..ops.flash_attn import flash_attention
-        y = flash_attention(
-            q, k, v, dropout_p=self.attn_pdrop if self.training else 0.0,
-            doc_ids=doc_ids)
-        y = y.transpose(1, 2).contiguous().view(B, T, C)
-        return self.c_proj(y)
+        # (causal bf16 hs=64), dropout included, SDPA otherwise. Without
+        # doc_ids the packed kernels take qkv as c_attn wrote it and
+        # return y as c_proj reads it; with doc_ids (ids [B, T] or the
+        # doc_bounds pair) the call still goes through flash_attention
+        # on [B, H, T, 64] views.
+        from ..ops.flash_attn import (flash_attention,
+                                      flash_attention_qkvpacked)
+        p = self.attn_pdrop if self.training else 0.0
+        if doc_ids is None:
+            return self.c_proj(
+                flash_attention_qkvpacked(qkv, self.n_head, dropout_p=p))
+        hs = C // self.n_head
+        q, k, v = (t.view(B, T, self.n_head, hs).transpose(1, 2)
+                   for t in qkv.split(C, dim=2))
+        y = flash_attention(q, k, v, dropout_p=p, doc_ids=doc_ids)
+        return self.c_proj(y.transpose(1, 2).contiguous().view(B, T, C))
 
 
 class MLP(nn.Module):

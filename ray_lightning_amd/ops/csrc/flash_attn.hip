@@ -22,13 +22,17 @@
 //
 // Host side (after the kernels): one set of operand checks, one forward
 // and one backward launcher, and the eight exported entry points
-// flash_attn_{fwd,bwd}_v3[_docs][_dropout] that ops/flash_attn.py calls.
+// flash_attn_{fwd,bwd}_v3[_docs][_dropout] that ops/flash_attn.py calls,
+// plus flash_attn_{fwd,bwd}_v3_packed for the packed-QKV layout (see
+// "operand layouts" below: the PACKED instantiations read q, k, v from
+// c_attn's [B, T, 3C] output and write o as [B, T, C], no copies).
 //
 // Last in the file: flash_fwd_v4_kernel / flash_attn_fwd_v4, the
 // 32x32x16 forward experiment (slower than v3, forward only, not wired
 // into ops/flash_attn.py).
 //
-// Layout: q, k, v are [B, H, T, 64] bf16 contiguous, T % 64 == 0.
+// Layout: q, k, v are [B, H, T, 64] bf16 contiguous (or, PACKED, the
+// three slots of one [B, T, 3*H*64] buffer), T % 64 == 0.
 // Causal only.
 // Fragment maps verified by mfma_probe (tests/test_flash_attn_gpu.py):
 //   A[16Mx32K]: lane l elem i -> row l&15,  k (l>>4)*8+i
@@ -116,6 +120,69 @@ __device__ __forceinline__ StageRegsR stage_r_load(
       src + (long)(row0 + r + 32) * HS + c0);
   return t;
 }
+
+// The same piece from rows that lie `rs` elements apart (PACKED, below).
+// The tile's two row groups start at wave-uniform addresses (row0 and rs
+// are uniform: SGPRs) and share ONE 32-bit per-lane offset, so the
+// stride costs the loop no VGPR beyond that offset.
+__device__ __forceinline__ StageRegsR stage_r_load_strided(
+    const __hip_bfloat16* src, int row0, int rs) {
+  const unsigned off =
+      (threadIdx.x >> 3) * (unsigned)rs + (threadIdx.x & 7) * 8;
+  const __hip_bfloat16* lo = src + (long)row0 * rs;
+  const __hip_bfloat16* hi = lo + 32L * rs;
+  StageRegsR t;
+  *reinterpret_cast<int4*>(&t.r0) =
+      *reinterpret_cast<const int4*>(lo + off);
+  *reinterpret_cast<int4*>(&t.r1) =
+      *reinterpret_cast<const int4*>(hi + off);
+  return t;
+}
+
+// --- operand layouts of the v3 kernels --------------------------------
+// PACKED = false: q, k, v, o, dout, dq, dk, dv are [B, H, T, 64]; head
+// bh = blockIdx.y owns T rows HS apart from bh*T*HS in each of them.
+// PACKED = true: q, k, v are slots 0, 1, 2 of ONE [B, T, 3C] buffer
+// (C = H*64: what GPT-2's c_attn writes), dq, dk, dv the slots of its
+// gradient, and o, dout are [B, T, C] (what c_proj reads): the kernels
+// get each slot's pointer, row t of head h of batch b lies at
+// (b*T + t)*3C + h*64 (o, dout: *C), and the grid is (T/64, H, B), so
+// that h and b need no division. lse and D are [B, H, T] in both, and bh
+// = b*H + h keeps the Philox group indices and the document bounds what
+// they are unpacked. Everything here is wave-uniform, and constant when
+// PACKED is false: those instantiations keep the stride of 64 and their
+// registers and occupancy (profiles/flash_attn_packed.md).
+template <bool PACKED>
+struct FlashRows {
+  int bh;            // b*H + h
+  int b;             // only read by DOCS
+  int in_rs;         // row stride of q, k, v, dq, dk, dv (elements)
+  int out_rs;        // row stride of o, dout
+  long in_base;      // first row of this head in a slot / in q
+  long out_base;
+  __device__ __forceinline__ FlashRows(int T, int H) {
+    if constexpr (PACKED) {
+      bh = blockIdx.z * H + blockIdx.y;
+      b = blockIdx.z;
+      in_rs = 3 * H * HS;
+      out_rs = H * HS;
+      in_base = (long)blockIdx.z * T * in_rs + blockIdx.y * HS;
+      out_base = (long)blockIdx.z * T * out_rs + blockIdx.y * HS;
+    } else {
+      bh = blockIdx.y;
+      b = bh / H;
+      in_rs = out_rs = HS;
+      in_base = out_base = (long)bh * T * HS;
+    }
+  }
+  // staging piece of a q/k/v tile (in_rs) or a dout tile (out_rs)
+  __device__ __forceinline__ StageRegsR stage(const __hip_bfloat16* src,
+                                              int row0, int rs) const {
+    if constexpr (PACKED) return stage_r_load_strided(src, row0, rs);
+    else return stage_r_load(src, row0);
+  }
+};
+
 
 // Row-major swizzled image (for A-fragment reads via read_frag_swz):
 // img[row][hs], b128 writes land in one granule each.
@@ -291,11 +358,13 @@ __device__ __forceinline__ int uniform_bound(const int* bnd, int pos) {
   return __builtin_amdgcn_readfirstlane(bnd[pos]);
 }
 
-template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false>
+template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false,
+          bool PACKED = false>
 // min 4 waves/EU: keeps the allocator at <=128 regs so occupancy stays
 // at the LDS-allowed 4 waves/SIMD (131 regs would drop it to 3). The
 // DOCS instantiations fit too (121-128 VGPRs, no scratch;
-// profiles/flash_attn_docs.md).
+// profiles/flash_attn_docs.md), and the PACKED ones
+// (profiles/flash_attn_packed.md).
 __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
     const __hip_bfloat16* __restrict__ Q,
     const __hip_bfloat16* __restrict__ K,
@@ -303,10 +372,11 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
     __hip_bfloat16* __restrict__ O, float* __restrict__ LSE,
     int T, float scale, DropArgs drop,
     const int* __restrict__ doc_start, int H) {
-  const int bh = blockIdx.y;
+  const FlashRows<PACKED> rows(T, H);
+  const int bh = rows.bh;
   const int qm0 = blockIdx.x * BM3;
   if (qm0 >= T) return;
-  const long base = (long)bh * T * HS;
+  const long base = rows.in_base;
   const __hip_bfloat16* q = Q + base;
   const __hip_bfloat16* k = K + base;
   const __hip_bfloat16* v = V + base;
@@ -326,7 +396,7 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
   bf16x8 qf[2];
   #pragma unroll
   for (int kk = 0; kk < 2; ++kk)
-    qf[kk] = load_frag_rowmajor(q, q0, kk, lane, HS);
+    qf[kk] = load_frag_rowmajor(q, q0, kk, lane, rows.in_rs);
 
   float m_i = kNegInf, l_i = 0.f;
   f32x4 o_acc[4];   // O^T: row d = 16*n + 4*g + r, col q (lane&15)
@@ -341,7 +411,7 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
   // the one that holds doc_start[qm0], clamped into [0, qm0]
   int mystart = 0, wstart_lo = 0, wstart_hi = 0, kv_begin = 0;
   if constexpr (DOCS) {
-    const int* ds = doc_start + (long)(bh / H) * T;
+    const int* ds = doc_start + (long)rows.b * T;
     mystart = ds[myq];
     wstart_lo = uniform_bound(ds, q0);
     wstart_hi = uniform_bound(ds, q0 + WQ - 1);
@@ -352,8 +422,8 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
   // keeps one tile in flight (issue loads -> compute current -> write
   // other buf)
   {
-    StageRegsR vt = stage_r_load(v, kv_begin);
-    StageRegsR kt = stage_r_load(k, kv_begin);
+    StageRegsR vt = rows.stage(v, kv_begin, rows.in_rs);
+    StageRegsR kt = rows.stage(k, kv_begin, rows.in_rs);
     stage_r_write(lds_v[0], vt);
     stage_r_write(lds_k[0], kt);
   }
@@ -361,8 +431,8 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
   int buf = 0;
   for (int kn0 = kv_begin; kn0 < kv_end; kn0 += BN, buf ^= 1) {
     const int next = (kn0 + BN < kv_end) ? kn0 + BN : kn0;
-    StageRegsR vt = stage_r_load(v, next);
-    StageRegsR kt = stage_r_load(k, next);
+    StageRegsR vt = rows.stage(v, next, rows.in_rs);
+    StageRegsR kt = rows.stage(k, next, rows.in_rs);
     // DOCS: a tile that ends before the wave's smallest start is dead
     // work for the whole wave, like one above the diagonal
     const bool active = kn0 <= q0 + WQ - 1 &&
@@ -561,9 +631,9 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
     const int c0 = (lane & 3) * 16;
     int4 t0 = *reinterpret_cast<const int4*>(ow + row * HS + c0);
     int4 t1 = *reinterpret_cast<const int4*>(ow + row * HS + c0 + 8);
-    *reinterpret_cast<int4*>(O + base + (long)(q0 + row) * HS + c0) = t0;
-    *reinterpret_cast<int4*>(
-        O + base + (long)(q0 + row) * HS + c0 + 8) = t1;
+    const long orow = rows.out_base + (long)(q0 + row) * rows.out_rs;
+    *reinterpret_cast<int4*>(O + orow + c0) = t0;
+    *reinterpret_cast<int4*>(O + orow + c0 + 8) = t1;
   }
   if (g == 0)
     LSE[(long)bh * T + myq] =
@@ -578,12 +648,10 @@ __global__ __launch_bounds__(256, 4) void flash_fwd_v3_kernel(
 
 // D = rowsum(dO * O), fp32 (shared by the DROPOUT instantiations: O
 // already carries the mask)
-__global__ __launch_bounds__(256) void flash_bwd_pre_kernel(
+__device__ __forceinline__ void flash_bwd_pre_row(
     const __hip_bfloat16* __restrict__ dO,
     const __hip_bfloat16* __restrict__ O, float* __restrict__ D,
-    long total_rows) {
-  const long row = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
-  if (row >= total_rows) return;
+    long row, long drow) {
   const int c0 = (threadIdx.x & 3) * 16;
   float s = 0.f;
   #pragma unroll
@@ -600,7 +668,30 @@ __global__ __launch_bounds__(256) void flash_bwd_pre_kernel(
   #pragma unroll
   for (int w = 1; w <= 2; w <<= 1)
     s += __shfl_xor(s, w, 64);
-  if ((threadIdx.x & 3) == 0) D[row] = s;
+  if ((threadIdx.x & 3) == 0) D[drow] = s;
+}
+
+__global__ __launch_bounds__(256) void flash_bwd_pre_kernel(
+    const __hip_bfloat16* __restrict__ dO,
+    const __hip_bfloat16* __restrict__ O, float* __restrict__ D,
+    long total_rows) {
+  const long row = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
+  if (row >= total_rows) return;
+  flash_bwd_pre_row(dO, O, D, row, row);
+}
+
+// dO, O [B, T, C] = [B, T, H, 64]: the 64-element rows are contiguous in
+// (b, t, h) order, D is [B, H, T]. Grid (T/64, H, B): a workgroup takes
+// 64 t of one head, so that its D values are one contiguous run.
+__global__ __launch_bounds__(256) void flash_bwd_pre_packed_kernel(
+    const __hip_bfloat16* __restrict__ dO,
+    const __hip_bfloat16* __restrict__ O, float* __restrict__ D,
+    int T, int H) {
+  const int t = blockIdx.x * 64 + (threadIdx.x >> 2);
+  if (t >= T) return;
+  flash_bwd_pre_row(dO, O, D,
+                    ((long)blockIdx.z * T + t) * H + blockIdx.y,
+                    ((long)blockIdx.z * H + blockIdx.y) * T + t);
 }
 
 // Batched variant for dkv: TWO 16-row blocks' transposed fragments
@@ -674,7 +765,8 @@ __device__ __forceinline__ unsigned quad_xchg(unsigned v) {
 //   dP[q][kv]  = mfma(dO_frag, V^T B-frag)
 //   dV^T[d][kv]= mfma(dO^T A-frag(lds), redist(P) B-frag)
 //   dK^T[d][kv]= mfma(Q^T  A-frag(lds), redist(dS) B-frag)
-template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false>
+template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false,
+          bool PACKED = false>
 // min 3 waves/EU (the LDS cap): the pair-batched tr reads push regs to
 // ~172 which rounds to 2 waves without the bound. Postmortem rule:
 // verified ScratchSize stays 0 under this bound (spills + hand asm
@@ -692,14 +784,15 @@ void flash_bwd_dkv_v3_kernel(
     __hip_bfloat16* __restrict__ dK, __hip_bfloat16* __restrict__ dV,
     int T, float scale, DropArgs drop,
     const int* __restrict__ doc_end, int H) {
-  const int bh = blockIdx.y;
+  const FlashRows<PACKED> rows(T, H);
+  const int bh = rows.bh;
   const int kb0 = blockIdx.x * BM3;      // 64 KV rows per workgroup
   if (kb0 >= T) return;
-  const long base = (long)bh * T * HS;
+  const long base = rows.in_base;
   const __hip_bfloat16* q = Qg + base;
   const __hip_bfloat16* k = Kg + base;
   const __hip_bfloat16* v = Vg + base;
-  const __hip_bfloat16* dO = dOg + base;
+  const __hip_bfloat16* dO = dOg + rows.out_base;
   const float* lse = LSE + (long)bh * T;
   const float* Drow = Dg + (long)bh * T;
 
@@ -719,8 +812,8 @@ void flash_bwd_dkv_v3_kernel(
   bf16x8 kf[2], vf[2];
   #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    kf[kk] = load_frag_rowmajor(k, kv0, kk, lane, HS);
-    vf[kk] = load_frag_rowmajor(v, kv0, kk, lane, HS);
+    kf[kk] = load_frag_rowmajor(k, kv0, kk, lane, rows.in_rs);
+    vf[kk] = load_frag_rowmajor(v, kv0, kk, lane, rows.in_rs);
   }
 
   f32x4 dv_acc[4], dk_acc[4];   // ^T: row d = 16n+4g+r, col kv
@@ -733,8 +826,8 @@ void flash_bwd_dkv_v3_kernel(
   const float l2e = 1.4426950408889634f;
 
   {  // prologue: first q tile through registers
-    StageRegsR dt = stage_r_load(dO, kb0);
-    StageRegsR qt = stage_r_load(q, kb0);
+    StageRegsR dt = rows.stage(dO, kb0, rows.out_rs);
+    StageRegsR qt = rows.stage(q, kb0, rows.in_rs);
     stage_r_write(lds_do[0], dt);
     stage_r_write(lds_q[0], qt);
     if (threadIdx.x < BN) {
@@ -748,7 +841,7 @@ void flash_bwd_dkv_v3_kernel(
   // holds doc_end[kb0 + 63], clamped into [kb0, T - 1]
   int myend = 0, wend_hi = 0, q_stop = T;
   if constexpr (DOCS) {
-    const int* de = doc_end + (long)(bh / H) * T;
+    const int* de = doc_end + (long)rows.b * T;
     myend = de[mykv];
     wend_hi = uniform_bound(de, kv0 + WQ - 1);
     const int e1 = uniform_bound(de, kb0 + BM3 - 1);
@@ -758,8 +851,8 @@ void flash_bwd_dkv_v3_kernel(
   int buf = 0;
   for (int qm0 = kb0; qm0 < q_stop; qm0 += BN, buf ^= 1) {
     const int next = (qm0 + BN < q_stop) ? qm0 + BN : qm0;
-    StageRegsR dt = stage_r_load(dO, next);
-    StageRegsR qt = stage_r_load(q, next);
+    StageRegsR dt = rows.stage(dO, next, rows.out_rs);
+    StageRegsR qt = rows.stage(q, next, rows.in_rs);
     float nlse = 0.f, nd = 0.f;
     if (threadIdx.x < BN) {
       nlse = lse[next + threadIdx.x];
@@ -922,10 +1015,9 @@ void flash_bwd_dkv_v3_kernel(
     wait_lds();
     int4 t0 = *reinterpret_cast<const int4*>(ew + erow * HS + ec0);
     int4 t1 = *reinterpret_cast<const int4*>(ew + erow * HS + ec0 + 8);
-    *reinterpret_cast<int4*>(
-        out + base + (long)(kv0 + erow) * HS + ec0) = t0;
-    *reinterpret_cast<int4*>(
-        out + base + (long)(kv0 + erow) * HS + ec0 + 8) = t1;
+    const long orow = base + (long)(kv0 + erow) * rows.in_rs;
+    *reinterpret_cast<int4*>(out + orow + ec0) = t0;
+    *reinterpret_cast<int4*>(out + orow + ec0 + 8) = t1;
     wait_lds();
   }
 }
@@ -971,7 +1063,8 @@ __device__ __forceinline__ void read_frag_tr_2col(const __bf16* img,
 //   S^T[kv][q]  = mfma(K_frag,  Q^T B-frag)
 //   dP^T[kv][q] = mfma(V_frag,  dO^T B-frag)
 //   dQ^T[d][q]  = mfma(K^T A-frag(lds), redist(dS^T) B-frag)
-template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false>
+template <bool USE_PERMLANE, bool DROPOUT = false, bool DOCS = false,
+          bool PACKED = false>
 // min 4 waves/EU: LDS allows 6, keep the allocator under 128 regs
 __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ Qg,
@@ -981,14 +1074,15 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
     const float* __restrict__ LSE, const float* __restrict__ Dg,
     __hip_bfloat16* __restrict__ dQ, int T, float scale,
     DropArgs drop, const int* __restrict__ doc_start, int H) {
-  const int bh = blockIdx.y;
+  const FlashRows<PACKED> rows(T, H);
+  const int bh = rows.bh;
   const int qm0 = blockIdx.x * BM3;
   if (qm0 >= T) return;
-  const long base = (long)bh * T * HS;
+  const long base = rows.in_base;
   const __hip_bfloat16* q = Qg + base;
   const __hip_bfloat16* k = Kg + base;
   const __hip_bfloat16* v = Vg + base;
-  const __hip_bfloat16* dO = dOg + base;
+  const __hip_bfloat16* dO = dOg + rows.out_base;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1003,8 +1097,8 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
   bf16x8 qf[2], dof[2];
   #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    qf[kk] = load_frag_rowmajor(q, q0, kk, lane, HS);
-    dof[kk] = load_frag_rowmajor(dO, q0, kk, lane, HS);
+    qf[kk] = load_frag_rowmajor(q, q0, kk, lane, rows.in_rs);
+    dof[kk] = load_frag_rowmajor(dO, q0, kk, lane, rows.out_rs);
   }
   const float lse_q = LSE[(long)bh * T + myq];
   const float d_q = Dg[(long)bh * T + myq];
@@ -1020,15 +1114,15 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
   // entry's exponent is -1e30 against the finite lse_q, so its dS is 0)
   int mystart = 0, wstart_lo = 0, kv_begin = 0;
   if constexpr (DOCS) {
-    const int* ds = doc_start + (long)(bh / H) * T;
+    const int* ds = doc_start + (long)rows.b * T;
     mystart = ds[myq];
     wstart_lo = uniform_bound(ds, q0);
     const int s0 = uniform_bound(ds, qm0);
     kv_begin = (s0 < 0 ? 0 : (s0 > qm0 ? qm0 : s0)) & ~(BN - 1);
   }
   {
-    StageRegsR kt = stage_r_load(k, kv_begin);
-    StageRegsR vt = stage_r_load(v, kv_begin);
+    StageRegsR kt = rows.stage(k, kv_begin, rows.in_rs);
+    StageRegsR vt = rows.stage(v, kv_begin, rows.in_rs);
     stage_r_write(lds_kk[0], kt);
     stage_r_write(lds_vv[0], vt);
   }
@@ -1036,8 +1130,8 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
   int buf = 0;
   for (int kn0 = kv_begin; kn0 < kv_end; kn0 += BN, buf ^= 1) {
     const int next = (kn0 + BN < kv_end) ? kn0 + BN : kn0;
-    StageRegsR kt = stage_r_load(k, next);
-    StageRegsR vt = stage_r_load(v, next);
+    StageRegsR kt = rows.stage(k, next, rows.in_rs);
+    StageRegsR vt = rows.stage(v, next, rows.in_rs);
     const bool active = kn0 <= q0 + WQ - 1 &&
                         (!DOCS || kn0 + BN - 1 >= wstart_lo);
     if (active) {
@@ -1126,10 +1220,9 @@ __global__ __launch_bounds__(256, 4) void flash_bwd_dq_v3_kernel(
   const int ec0 = (lane & 3) * 16;
   int4 t0 = *reinterpret_cast<const int4*>(ew + erow * HS + ec0);
   int4 t1 = *reinterpret_cast<const int4*>(ew + erow * HS + ec0 + 8);
-  *reinterpret_cast<int4*>(
-      dQ + base + (long)(q0 + erow) * HS + ec0) = t0;
-  *reinterpret_cast<int4*>(
-      dQ + base + (long)(q0 + erow) * HS + ec0 + 8) = t1;
+  const long orow = base + (long)(q0 + erow) * rows.in_rs;
+  *reinterpret_cast<int4*>(dQ + orow + ec0) = t0;
+  *reinterpret_cast<int4*>(dQ + orow + ec0 + 8) = t1;
 }
 
 // =====================================================================
@@ -1186,12 +1279,41 @@ void check_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q,
 // its layout is checked: the kernels never index with its values (see
 // "document masking" above).
 void check_flash_bound(const torch::Tensor& t, const torch::Tensor& q,
-                       const char* what) {
+                       const char* what, int t_dim = 2) {
   TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() &&
                   t.device() == q.device() && t.dim() == 2 &&
-                  t.size(0) == q.size(0) && t.size(1) == q.size(2),
+                  t.size(0) == q.size(0) && t.size(1) == q.size(t_dim),
               "flash_attn_v3: ", what,
               " must be int32 contiguous [B,T] on q's device");
+}
+
+// The packed layout's operands (see FlashRows): qkv [B, T, 3*H*64], and
+// o, dout [B, T, H*64]. The grid carries H in y and B in z.
+void check_flash_qkv(const torch::Tensor& qkv, int64_t H, double p) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 &&
+                  qkv.is_contiguous(),
+              "flash_attn_v3_packed: qkv must be a bf16 contiguous GPU "
+              "tensor");
+  TORCH_CHECK(qkv.dim() == 3 && H > 0 && qkv.size(2) == 3 * H * HS,
+              "flash_attn_v3_packed: [B,T,3*H*64] expected");
+  TORCH_CHECK(qkv.size(1) % BM3 == 0 && qkv.size(1) > 0,
+              "flash_attn_v3_packed: T % 64 == 0");
+  TORCH_CHECK(qkv.size(0) > 0 && qkv.size(0) * H <= 65535,
+              "flash_attn_v3_packed: B*H > 65535");
+  TORCH_CHECK(p >= 0.0 && p < 1.0,
+              "flash_attn_v3_packed: p must be in [0, 1)");
+}
+
+void check_flash_packed_out(const torch::Tensor& t,
+                            const torch::Tensor& qkv, int64_t H,
+                            const char* what) {
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == qkv.size(0) &&
+                  t.size(1) == qkv.size(1) && t.size(2) == H * HS &&
+                  t.scalar_type() == qkv.scalar_type() &&
+                  t.device() == qkv.device() && t.is_contiguous(),
+              "flash_attn_v3_packed: ", what,
+              " must be contiguous [B,T,H*64] with qkv's dtype and "
+              "device");
 }
 
 const __hip_bfloat16* bf16_in(const torch::Tensor& t) {
@@ -1213,8 +1335,18 @@ __hip_bfloat16* bf16_out(torch::Tensor& t) {
                 : ((pl) ? KERNEL<true, false, false>                     \
                         : KERNEL<false, false, false>)))
 
+// ... and the four PACKED ones of a kernel (permlane only)
+#define RLA_PICK_V3_PACKED(KERNEL, dr, dc)                               \
+  ((dc) ? ((dr) ? KERNEL<true, true, true, true>                         \
+                : KERNEL<true, false, true, true>)                       \
+        : ((dr) ? KERNEL<true, true, false, true>                        \
+                : KERNEL<true, false, false, true>))
+
 const int* bound_ptr(const torch::Tensor* t) {
   return t ? t->data_ptr<int>() : nullptr;
+}
+const torch::Tensor* opt_ptr(const c10::optional<torch::Tensor>& t) {
+  return t.has_value() ? &t.value() : nullptr;
 }
 
 // Operands are already checked. Returns (o, lse); with dropout, lse is
@@ -1282,6 +1414,65 @@ std::vector<torch::Tensor> launch_flash_bwd(
   return {dq, dk, dv};
 }
 
+// The packed layout's launchers: operands are already checked. q, k, v
+// are the slots of qkv, o is [B, T, C]; nothing is copied.
+std::pair<torch::Tensor, torch::Tensor> launch_flash_fwd_packed(
+    const torch::Tensor& qkv, int H, double scale, const DropArgs& drop,
+    bool dropout, const torch::Tensor* doc_start) {
+  const int B = (int)qkv.size(0), T = (int)qkv.size(1);
+  const long C = (long)H * HS;
+  auto o = torch::empty({B, T, C}, qkv.options());
+  auto lse = torch::empty({B, H, T}, qkv.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto* kern = RLA_PICK_V3_PACKED(flash_fwd_v3_kernel, dropout,
+                                  doc_start != nullptr);
+  const __hip_bfloat16* p = bf16_in(qkv);
+  hipLaunchKernelGGL(kern, dim3(T / BM3, H, B), dim3(256), 0, stream, p,
+                     p + C, p + 2 * C, bf16_out(o),
+                     lse.data_ptr<float>(), T, (float)scale, drop,
+                     bound_ptr(doc_start), H);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "flash_fwd_v3_packed: ",
+              hipGetErrorString(e));
+  return {o, lse};
+}
+
+// D, then dK/dV into slots 1 and 2 of dqkv, then dQ into slot 0: the
+// two kernels write every element of it.
+torch::Tensor launch_flash_bwd_packed(
+    const torch::Tensor& dout, const torch::Tensor& qkv,
+    const torch::Tensor& o, const torch::Tensor& lse, int H,
+    double scale, const DropArgs& drop, bool dropout,
+    const torch::Tensor* doc_start, const torch::Tensor* doc_end) {
+  const bool docs = doc_start != nullptr;
+  const int B = (int)qkv.size(0), T = (int)qkv.size(1);
+  const long C = (long)H * HS;
+  auto dqkv = torch::empty_like(qkv);
+  auto D = torch::empty({B, H, T}, qkv.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  dim3 grid(T / BM3, H, B);
+  hipLaunchKernelGGL(flash_bwd_pre_packed_kernel, grid, dim3(256), 0,
+                     stream, bf16_in(dout), bf16_in(o),
+                     D.data_ptr<float>(), T, H);
+  auto* kdkv =
+      RLA_PICK_V3_PACKED(flash_bwd_dkv_v3_kernel, dropout, docs);
+  auto* kdq = RLA_PICK_V3_PACKED(flash_bwd_dq_v3_kernel, dropout, docs);
+  const __hip_bfloat16* p = bf16_in(qkv);
+  __hip_bfloat16* g = bf16_out(dqkv);
+  hipLaunchKernelGGL(kdkv, grid, dim3(256), 0, stream, p, p + C,
+                     p + 2 * C, bf16_in(dout), lse.data_ptr<float>(),
+                     D.data_ptr<float>(), g + C, g + 2 * C, T,
+                     (float)scale, drop, bound_ptr(doc_end), H);
+  hipLaunchKernelGGL(kdq, grid, dim3(256), 0, stream, p, p + C,
+                     p + 2 * C, bf16_in(dout), lse.data_ptr<float>(),
+                     D.data_ptr<float>(), g, T, (float)scale, drop,
+                     bound_ptr(doc_start), H);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "flash_bwd_v3_packed: ",
+              hipGetErrorString(e));
+  return dqkv;
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
@@ -1309,21 +1500,24 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(
 // offset) from the default generator of q's device, exactly as
 // fused_ln_fwd does for p > 0, and returns (o, lse, seed, offset).
 namespace {
+// (seed, offset) of one forward's mask, from the default generator of
+// q's device
+std::pair<uint64_t, uint64_t> draw_flash_seed(const torch::Tensor& q) {
+  // graph-capture-safe RNG (device-side offset) is not implemented
+  at::cuda::assertNotCapturing(
+      "flash_attn_v3_dropout: drawing the dropout seed");
+  auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
+      c10::nullopt,
+      at::cuda::detail::getDefaultCUDAGenerator(q.get_device()));
+  std::lock_guard<std::mutex> lock(gen->mutex_);
+  return gen->philox_engine_inputs(4);
+}
+
 std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
 flash_fwd_dropout(const torch::Tensor& q, const torch::Tensor& k,
                   const torch::Tensor& v, double scale, double p,
                   bool use_permlane, const torch::Tensor* doc_start) {
-  // graph-capture-safe RNG (device-side offset) is not implemented
-  at::cuda::assertNotCapturing(
-      "flash_attn_v3_dropout: drawing the dropout seed");
-  std::pair<uint64_t, uint64_t> rng;
-  {
-    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
-        c10::nullopt,
-        at::cuda::detail::getDefaultCUDAGenerator(q.get_device()));
-    std::lock_guard<std::mutex> lock(gen->mutex_);
-    rng = gen->philox_engine_inputs(4);
-  }
+  const std::pair<uint64_t, uint64_t> rng = draw_flash_seed(q);
   auto [o, lse] = launch_flash_fwd(
       q, k, v, scale, make_drop_args(p, rng.first, rng.second), true,
       use_permlane, doc_start);
@@ -1400,6 +1594,56 @@ std::vector<torch::Tensor> flash_attn_bwd_v3_docs_dropout(
   return launch_flash_bwd(dout, q, k, v, o, lse, scale,
                           make_drop_args(p, seed, offset), true,
                           use_permlane, &doc_start, &doc_end);
+}
+
+// Packed layout (FlashRows): qkv [B, T, 3*H*64] in, o [B, T, H*64] out,
+// all four modes behind one pair of entry points. p == 0 consumes no
+// generator state and returns (seed, offset) = (0, 0); p > 0 draws them
+// as flash_fwd_dropout does, so one generator state gives one mask in
+// both layouts. doc_start (and doc_end in backward) select DOCS.
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_packed(torch::Tensor qkv, int64_t H, double scale,
+                         double p,
+                         c10::optional<torch::Tensor> doc_start) {
+  check_flash_qkv(qkv, H, p);
+  if (doc_start.has_value())
+    check_flash_bound(*doc_start, qkv, "doc_start", 1);
+  std::pair<uint64_t, uint64_t> rng{0, 0};
+  DropArgs drop{};
+  if (p > 0.0) {
+    rng = draw_flash_seed(qkv);
+    drop = make_drop_args(p, rng.first, rng.second);
+  }
+  auto [o, lse] = launch_flash_fwd_packed(qkv, (int)H, scale, drop,
+                                          p > 0.0, opt_ptr(doc_start));
+  return {o, lse, rng.first, rng.second};
+}
+
+// dout is the caller's dout.contiguous(). Returns dqkv [B, T, 3*H*64].
+torch::Tensor flash_attn_bwd_v3_packed(
+    torch::Tensor dout, torch::Tensor qkv, torch::Tensor o,
+    torch::Tensor lse, int64_t H, double scale, double p, uint64_t seed,
+    uint64_t offset, c10::optional<torch::Tensor> doc_start,
+    c10::optional<torch::Tensor> doc_end) {
+  check_flash_qkv(qkv, H, p);
+  check_flash_packed_out(o, qkv, H, "o");
+  check_flash_packed_out(dout, qkv, H, "dout");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.device() == qkv.device() &&
+                  lse.numel() == qkv.size(0) * H * qkv.size(1),
+              "flash_attn_v3_packed: lse must be fp32 [B,H,T] on qkv's "
+              "device");
+  TORCH_CHECK(doc_start.has_value() == doc_end.has_value(),
+              "flash_attn_v3_packed: doc_start and doc_end come "
+              "together");
+  if (doc_start.has_value()) {
+    check_flash_bound(*doc_start, qkv, "doc_start", 1);
+    check_flash_bound(*doc_end, qkv, "doc_end", 1);
+  }
+  return launch_flash_bwd_packed(
+      dout, qkv, o, lse, (int)H, scale,
+      p > 0.0 ? make_drop_args(p, seed, offset) : DropArgs{}, p > 0.0,
+      opt_ptr(doc_start), opt_ptr(doc_end));
 }
 
 // =====================================================================

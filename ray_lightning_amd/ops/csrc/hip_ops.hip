@@ -1050,6 +1050,15 @@ std::vector<torch::Tensor> flash_attn_bwd_v3_docs_dropout(
     torch::Tensor v, torch::Tensor o, torch::Tensor lse,
     torch::Tensor doc_start, torch::Tensor doc_end, double scale,
     double p, uint64_t seed, uint64_t offset, bool use_permlane);
+std::tuple<torch::Tensor, torch::Tensor, uint64_t, uint64_t>
+flash_attn_fwd_v3_packed(torch::Tensor qkv, int64_t H, double scale,
+                         double p,
+                         c10::optional<torch::Tensor> doc_start);
+torch::Tensor flash_attn_bwd_v3_packed(
+    torch::Tensor dout, torch::Tensor qkv, torch::Tensor o,
+    torch::Tensor lse, int64_t H, double scale, double p, uint64_t seed,
+    uint64_t offset, c10::optional<torch::Tensor> doc_start,
+    c10::optional<torch::Tensor> doc_end);
 std::vector<torch::Tensor> flash_attn_fwd_v4(torch::Tensor q,
                                              torch::Tensor k,
                                              torch::Tensor v,
@@ -1240,6 +1249,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "v3 flash attention fwd with document masking and dropout");
   m.def("flash_attn_bwd_v3_docs_dropout", &flash_attn_bwd_v3_docs_dropout,
         "v3 flash attention bwd with document masking and dropout");
+  m.def("flash_attn_fwd_v3_packed", &flash_attn_fwd_v3_packed,
+        "v3 flash attention fwd on packed qkv [B,T,3C] -> o [B,T,C]",
+        py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("p"),
+        py::arg("doc_start") = py::none());
+  m.def("flash_attn_bwd_v3_packed", &flash_attn_bwd_v3_packed,
+        "v3 flash attention bwd on packed qkv -> dqkv [B,T,3C]",
+        py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"),
+        py::arg("H"), py::arg("scale"), py::arg("p"), py::arg("seed"),
+        py::arg("offset"), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("conv1x1_bwd_data", &conv1x1_bwd_data,
         "dx = dy . w (+ skip) for a 1x1 stride-1 NHWC bf16 convolution",
         pybind11::arg("dy"), pybind11::arg("w"),

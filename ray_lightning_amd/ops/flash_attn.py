@@ -35,9 +35,24 @@ whether by default is ``_DOCS_DEFAULT`` below, and ``RLA_FLASH_DOCS=1``
 / ``=0`` forces them on / off. Otherwise (CPU included) the call goes
 through SDPA with the boolean [B, 1, T, T] mask built from the bounds.
 
+Packed QKV: ``flash_attention_qkvpacked(qkv, n_head)`` takes what
+GPT-2's ``c_attn`` writes, ``qkv`` [B, T, 3*C] with q, k, v in that
+order and head ``h`` at columns ``h*64`` of its slot, and returns what
+``c_proj`` reads, [B, T, C]. The PACKED instantiations of the v3 kernels
+read and write those layouts directly (row stride 3*C or C in place of
+64) and the backward writes one ``dqkv`` [B, T, 3*C]: none of the nine
+transpose / ``cat`` copies per layer that the [B, H, T, 64] interface
+costs, and ``o`` is saved once (docs/DESIGN.md §14,
+profiles/flash_attn_packed.md). Dropout and ``doc_ids`` work as above,
+on the same mask bits. They engage under the conditions above, stated on
+``qkv``; whether by default is ``_PACKED_DEFAULT`` below, and
+``RLA_FLASH_PACKED=1`` / ``=0`` forces them on / off. Otherwise the call
+splits and transposes and goes through ``flash_attention``.
+
 ``RLA_FLASH=0`` disables the custom path; ``RLA_FLASH_SHFL=1`` selects
 the ds_bpermute redistribution variant (debug), for the dropout kernels
-too.
+too; there are no packed kernels of that variant, so it also takes the
+unpacked path.
 """
 from __future__ import annotations
 
@@ -56,6 +71,13 @@ _DROPOUT_DEFAULT = True
 # Set by the measurement in profiles/flash_attn_docs.md: the DOCS
 # kernels are the default iff they beat SDPA with the boolean mask there.
 _DOCS_DEFAULT = True
+
+# Set by the measurement in profiles/flash_attn_packed.md: the packed
+# kernels are the default iff they beat the composed path (copies, the
+# unpacked kernels, cat) at op level by more than either range AND the
+# GPT-2 step is not slower with them. Both held: 0.783 ms against
+# 1.107 ms, and 68.3k against 64.0k tokens/s.
+_PACKED_DEFAULT = True
 
 
 def _usable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
@@ -90,6 +112,13 @@ def _docs_kernels_enabled() -> bool:
     return env == "1"
 
 
+def _packed_kernels_enabled() -> bool:
+    env = os.environ.get("RLA_FLASH_PACKED")
+    if env is None:
+        return _PACKED_DEFAULT
+    return env == "1"
+
+
 def doc_bounds(doc_ids: torch.Tensor):
     """``(doc_start, doc_end)``, int32 [B, T], from integer ``doc_ids``
     [B, T]: the first and the last position of the document that holds
@@ -119,6 +148,11 @@ def doc_bounds(doc_ids: torch.Tensor):
 def _as_bounds(doc_ids, q: torch.Tensor):
     """The ``(doc_start, doc_end)`` pair of a ``doc_ids`` argument: ids
     [B, T], or the precomputed pair."""
+    return _bounds_for(doc_ids, q.shape[0], q.shape[2], q.device)
+
+
+def _bounds_for(doc_ids, B: int, T: int, device):
+    """``_as_bounds`` from the extents themselves."""
     if isinstance(doc_ids, (tuple, list)):
         if len(doc_ids) != 2:
             raise ValueError("doc_ids: expected ids or (doc_start, doc_end)")
@@ -128,14 +162,14 @@ def _as_bounds(doc_ids, q: torch.Tensor):
                 raise ValueError("doc_ids: bounds must be integer tensors")
     else:
         start, end = doc_bounds(doc_ids)
-    want = (q.shape[0], q.shape[2])
+    want = (B, T)
     for t in (start, end):
         if t.dim() != 2 or tuple(t.shape) != want:
             raise ValueError(
                 f"doc_ids must have shape [B, T] = {list(want)}, got "
                 f"{list(t.shape)}")
-    return (start.to(device=q.device, dtype=torch.int32).contiguous(),
-            end.to(device=q.device, dtype=torch.int32).contiguous())
+    return (start.to(device=device, dtype=torch.int32).contiguous(),
+            end.to(device=device, dtype=torch.int32).contiguous())
 
 
 def doc_mask(doc_start: torch.Tensor) -> torch.Tensor:
@@ -285,3 +319,88 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         scale = 1.0 / math.sqrt(q.shape[-1])
         return _FlashAttn.apply(q, k, v, scale)
     return F.scaled_dot_product_attention(q, k, v, is_causal=True)
+
+
+class _FlashAttnPacked(torch.autograd.Function):
+    """All four modes on the PACKED instantiations: ``qkv`` [B, T, 3C]
+    in, ``o`` [B, T, C] out, ``dqkv`` back. Saves ``qkv``, ``o``, ``lse``
+    and the bounds (empty tensors without ``doc_ids``); the mask lives on
+    as ``(p, seed, offset)``."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_head, scale, p, doc_start, doc_end):
+        ext = _load_ext()
+        o, lse, seed, offset = ext.flash_attn_fwd_v3_packed(
+            qkv, n_head, scale, p, doc_start)
+        if doc_start is None:
+            ctx.save_for_backward(qkv, o, lse)
+        else:
+            ctx.save_for_backward(qkv, o, lse, doc_start, doc_end)
+        ctx.n_head, ctx.scale = n_head, scale
+        ctx.p, ctx.seed, ctx.offset = p, seed, offset
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, o, lse, *bounds = ctx.saved_tensors
+        doc_start, doc_end = bounds if bounds else (None, None)
+        ext = _load_ext()
+        dqkv = ext.flash_attn_bwd_v3_packed(
+            dout.contiguous(), qkv, o, lse, ctx.n_head, ctx.scale, ctx.p,
+            ctx.seed, ctx.offset, doc_start, doc_end)
+        return dqkv, None, None, None, None, None
+
+
+def _packed_usable(qkv: torch.Tensor, n_head: int, dropout_p: float,
+                   docs: bool) -> bool:
+    """``_usable``'s conditions on ``qkv``, the host path's limits on
+    ``B`` and ``H``, and the gates."""
+    if os.environ.get("RLA_FLASH", "1") == "0":
+        return False
+    if not (_packed_kernels_enabled() and _use_permlane()):
+        return False
+    if dropout_p > 0.0 and not _dropout_kernels_enabled():
+        return False
+    if docs and not _docs_kernels_enabled():
+        return False
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and qkv.shape[2] == 3 * n_head * 64
+            and qkv.shape[1] % 64 == 0 and qkv.shape[1] > 0
+            and 0 < qkv.shape[0] * n_head <= 65535
+            and _load_ext() is not None)
+
+
+def flash_attention_qkvpacked(qkv: torch.Tensor, n_head: int,
+                              dropout_p: float = 0.0,
+                              doc_ids=None) -> torch.Tensor:
+    """Causal attention from ``qkv`` [B, T, 3*C] (q, k, v slots of width
+    ``C = n_head * hs``) to [B, T, C]: ``flash_attention`` without the
+    layout copies around it (module docstring). ``dropout_p`` and
+    ``doc_ids`` are ``flash_attention``'s, errors included. Raises
+    ``ValueError`` for a ``qkv`` that is not 3-dimensional or whose last
+    dimension is not divisible by ``3 * n_head``."""
+    if qkv.dim() != 3:
+        raise ValueError(
+            f"qkv must be [B, T, 3*C], got {list(qkv.shape)}")
+    B, T, C3 = qkv.shape
+    if n_head <= 0 or C3 % (3 * n_head) != 0:
+        raise ValueError(
+            f"qkv's last dimension {C3} is not divisible by 3 * n_head "
+            f"= {3 * n_head}")
+    _check_p(dropout_p)
+    C = C3 // 3
+    hs = C // n_head
+    if _packed_usable(qkv, n_head, dropout_p, doc_ids is not None):
+        if not hasattr(_load_ext(), "flash_attn_fwd_v3_packed"):
+            raise RuntimeError(
+                "_hip_ops has no flash_attn_fwd_v3_packed: rebuild with "
+                "`python -m ray_lightning_amd.ops.build`")
+        doc_start, doc_end = (None, None) if doc_ids is None \
+            else _bounds_for(doc_ids, B, T, qkv.device)
+        return _FlashAttnPacked.apply(
+            qkv.contiguous(), n_head, 1.0 / math.sqrt(hs),
+            float(dropout_p), doc_start, doc_end)
+    q, k, v = (t.view(B, T, n_head, hs).transpose(1, 2)
+               for t in qkv.split(C, dim=2))
+    y = flash_attention(q, k, v, dropout_p=dropout_p, doc_ids=doc_ids)
+    return y.transpose(1, 2).contiguous().view(B, T, C)
