@@ -23,7 +23,11 @@ Generation: ``GPT2.generate`` samples from the model with a KV cache
 (ops/decode_attn.py): one prefill forward over the prompts on the flash
 kernels, then one token per row per step through the split-KV decode
 attention kernel, which also appends to the cache. ``forward(idx,
-cache=...)`` is the same machinery one call at a time.
+cache=...)`` is the same machinery one call at a time, and
+``forward(idx, cache=..., extend=True)`` appends ``T`` tokens per row to
+a filled cache through the MFMA append kernel (ops/append_attn.py): the
+next turn of a conversation, a slice of a chunked prefill
+(``generate(prefill_chunk=)``), drafted tokens to verify.
 """
 from __future__ import annotations
 
@@ -84,14 +88,21 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x, doc_ids=None, cache=None):
+    def forward(self, x, doc_ids=None, cache=None, extend=False):
         """``cache`` is this layer's ``(k_cache, v_cache, kv)`` of a
         ``KVCache`` ``kv``. Before the prefill the call attends as it
         does without a cache and copies its k and v into the caches at
         ``[:, :, :T]``; after it, ``x`` is one new token per row and
-        attention is ``decode_attention`` over the cache."""
+        attention is ``decode_attention`` over the cache, or, with
+        ``extend``, ``T`` new tokens per row and ``append_attention``."""
         B, T, C = x.shape
         qkv = self.c_attn(x)
+        if extend:
+            from ..ops.append_attn import append_attention
+            k_cache, v_cache, kv = cache
+            y = append_attention(qkv, k_cache, v_cache, kv.pos, kv.max_pos,
+                                 self.n_head)
+            return self.c_proj(y)
         if cache is not None and cache[2].prefilled:
             from ..ops.decode_attn import decode_attention
             k_cache, v_cache, kv = cache
@@ -191,7 +202,7 @@ class GPT2(nn.Module):
     def forward(self, idx: torch.Tensor,
                 targets: Optional[torch.Tensor] = None,
                 doc_ids: Optional[torch.Tensor] = None,
-                cache=None):
+                cache=None, extend: bool = False):
         """``doc_ids`` (integer [B, T], e.g. from ``document_ids``) marks
         the documents of packed rows: attention stays within a document
         and positions restart at each document's first token, so a
@@ -202,8 +213,25 @@ class GPT2(nn.Module):
         also fills the cache and sets every row's length to ``T``; each
         later call takes one new token per row, ``idx`` [B, 1], at the
         rows' own positions ``cache.pos`` and returns its logits
-        [B, 1, V]."""
-        x = self._hidden(idx, doc_ids, cache)
+        [B, 1, V].
+
+        ``extend=True`` (needs a filled cache) appends ``idx`` [B, T],
+        ``T >= 1``, to every row instead: token ``t`` of row ``b`` sits
+        at position ``cache.pos[b] + t`` and attends the row's cache and
+        the new tokens up to itself (ops/append_attn.py). The cache
+        advances by ``T`` and the logits are [B, T, V]. Raises
+        ``ValueError`` when ``cache.max_pos + T`` exceeds ``cache.Tmax``
+        or ``n_positions``.
+
+        Multi-turn recipe, for rows that append fewer than ``T`` real
+        tokens: right-pad them to ``T``, call with ``extend=True``, read
+        row ``b``'s logits at ``[:n_b]``, then ``cache.set_lengths(old_pos
+        + n, max(old_pos + n))`` with the true counts ``n`` [B]. As in
+        the prefill, the pad tokens sit after the real ones, so no real
+        token attends them, and their cache slots lie at or above the
+        row's new length: they are overwritten before they are ever
+        attended."""
+        x = self._hidden(idx, doc_ids, cache, extend)
         if targets is not None:
             # chunked LM-head + CE: never materializes the [B*T, V]
             # logits (ops/chunked_ce.py); identical numerics to
@@ -219,11 +247,21 @@ class GPT2(nn.Module):
             return None, loss
         return self.lm_head(x), None
 
-    def _hidden(self, idx, doc_ids=None, cache=None):
+    def _hidden(self, idx, doc_ids=None, cache=None, extend=False):
         """``ln_f`` of the last block's output, [B, T, C]: forward
         without the LM head."""
         B, T = idx.shape
-        decode = cache is not None and cache.prefilled
+        if extend:
+            if cache is None or not cache.prefilled:
+                raise ValueError("extend=True needs a filled cache")
+            if T < 1:
+                raise ValueError("extend=True needs T >= 1 tokens per row")
+            if cache.max_pos + T > min(cache.Tmax, self.cfg.n_positions):
+                raise ValueError(
+                    f"{cache.max_pos} cached + {T} new tokens exceed the "
+                    f"cache's {cache.Tmax} or the model's "
+                    f"{self.cfg.n_positions} positions")
+        decode = cache is not None and cache.prefilled and not extend
         if cache is not None:
             if doc_ids is not None:
                 raise ValueError("doc_ids and cache do not combine")
@@ -232,10 +270,14 @@ class GPT2(nn.Module):
                     f"a decode step takes one token per row, got T = {T}")
             # a decode step writes slot max_pos at the furthest, the
             # prefill slots 0 .. T-1
-            if (cache.max_pos + 1 if decode else T) > cache.Tmax:
+            if not extend and \
+                    (cache.max_pos + 1 if decode else T) > cache.Tmax:
                 raise ValueError(
                     f"the cache holds {cache.Tmax} positions per row")
-        if decode:
+        if extend:
+            pos = cache.pos.to(torch.int64)[:, None] + \
+                torch.arange(T, device=idx.device)
+        elif decode:
             pos = cache.pos.to(torch.int64)[:, None]
         else:
             pos = torch.arange(T, device=idx.device)
@@ -266,13 +308,15 @@ class GPT2(nn.Module):
                 attn_out = block.attn(h, bounds)
             else:
                 attn_out = block.attn(
-                    h, None, (cache.k[i], cache.v[i], cache))
+                    h, None, (cache.k[i], cache.v[i], cache), extend)
             x, h = block.ln_2(attn_out, residual=x, dropout_p=pr)
             mlp_out = block.mlp(h)
             next_ln = (self.h[i + 1].ln_1 if i + 1 < len(self.h)
                        else self.ln_f)
             x, h = next_ln(mlp_out, residual=x, dropout_p=pr)
-        if decode:
+        if extend:
+            cache.advance(T)
+        elif decode:
             cache.advance()
         elif cache is not None:
             cache.set_lengths(
@@ -291,6 +335,40 @@ class GPT2(nn.Module):
         probs = torch.softmax(logits, dim=-1)
         return torch.multinomial(probs, 1, generator=generator)[:, 0]
 
+    def _prefill_in_slices(self, prompt, c, cache, lens_dev, max_len,
+                           pad_token_id):
+        """The prompts into ``cache`` ``c`` positions at a time: the first
+        slice through the prefill (padded up to the flash tile of 64, as
+        the whole prompt is without slices), the others through
+        ``extend``. After each slice the rows' lengths are put to what
+        they really hold, so a row whose prompt has ended keeps its
+        length while the others grow; what the slice wrote above it is
+        overwritten before it is attended. Returns ``ln_f``'s output at
+        each row's last prompt token, [B, C]."""
+        B = prompt.shape[0]
+        rows = torch.arange(B, device=prompt.device)
+        last = lens_dev - 1
+
+        def settle(done):
+            cache.set_lengths(lens_dev.clamp(max=done).to(torch.int32),
+                              min(max_len, done))
+
+        c0 = min(c, max_len)
+        c0_pad = min(-(-c0 // 64) * 64, prompt.shape[1])
+        first = prompt[:, :c0_pad].clone()
+        first[:, c0:] = pad_token_id
+        h = self._hidden(first, None, cache)
+        settle(c0)
+        out = h[rows, last.clamp(max=c0 - 1)]
+        for s in range(c0, max_len, c):
+            n = min(c, max_len - s)
+            h = self._hidden(prompt[:, s:s + n], None, cache, extend=True)
+            settle(s + n)
+            here = (last >= s) & (last < s + n)
+            out = torch.where(here[:, None],
+                              h[rows, (last - s).clamp(0, n - 1)], out)
+        return out
+
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, *,
                  prompt_lens=None, temperature: float = 1.0,
@@ -298,7 +376,8 @@ class GPT2(nn.Module):
                  eos_token_id: Optional[int] = None,
                  pad_token_id: int = 0,
                  generator: Optional[torch.Generator] = None,
-                 return_logits: bool = False):
+                 return_logits: bool = False,
+                 prefill_chunk: Optional[int] = None):
         """Sample ``max_new_tokens`` tokens per row after the prompts.
 
         ``idx`` [B, P] holds the prompts, right-padded; ``prompt_lens``
@@ -326,6 +405,12 @@ class GPT2(nn.Module):
         early stop). That tensor is for tests and small vocabularies: at
         GPT-2's vocabulary it is 200 KB per row and step.
 
+        ``prefill_chunk=c`` bounds the prefill's activation memory: the
+        first ``c`` prompt positions go through the flash prefill, the
+        rest in slices of ``c`` through ``extend`` over the cache. The LM
+        head still runs on the ``B`` rows at ``prompt_lens - 1`` only.
+        The default (``None``) is the single prefill forward.
+
         Runs without gradients, in eval mode; the module's mode is put
         back afterwards."""
         from ..ops.decode_attn import KVCache, decode_attn_chunk
@@ -335,6 +420,8 @@ class GPT2(nn.Module):
         B, P = idx.shape
         if max_new_tokens < 0:
             raise ValueError("max_new_tokens must be >= 0")
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError("prefill_chunk must be >= 1")
         if prompt_lens is None:
             lens = [P] * B
         else:
@@ -370,19 +457,24 @@ class GPT2(nn.Module):
             prompt = out.new_full((B, P_pad), pad_token_id)
             prompt[:, :P] = out[:, :P]
             cache = None
-            if max_new_tokens > 1:
+            if max_new_tokens > 1 or prefill_chunk is not None:
                 chunk = decode_attn_chunk()
                 Tmax = -(-(max_len + max_new_tokens) // chunk) * chunk
                 Tmax = max(min(Tmax, cfg.n_positions), P_pad)
                 p0 = self.wte.weight
                 cache = KVCache(cfg.n_layer, B, cfg.n_head, Tmax,
                                 cfg.n_embd // cfg.n_head, p0.dtype, dev)
-            h = self._hidden(prompt, None, cache)
-            if cache is not None:
-                # pad positions in the cache are overwritten as the row
-                # grows, and never attended before that
-                cache.set_lengths(lens_dev.to(torch.int32), max_len)
-            h = h[torch.arange(B, device=dev), lens_dev - 1]
+            rows = torch.arange(B, device=dev)
+            if prefill_chunk is None:
+                h = self._hidden(prompt, None, cache)
+                if cache is not None:
+                    # pad positions in the cache are overwritten as the
+                    # row grows, and never attended before that
+                    cache.set_lengths(lens_dev.to(torch.int32), max_len)
+                h = h[rows, lens_dev - 1]
+            else:
+                h = self._prefill_in_slices(prompt, prefill_chunk, cache,
+                                            lens_dev, max_len, pad_token_id)
             logits = self.lm_head(h).float()
 
             finished = torch.zeros(B, dtype=torch.bool, device=dev)

@@ -18,6 +18,8 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
   ignore_index, label smoothing and z-loss (``chunked_ce.py``)
 - single-token attention over a KV cache, split along the KV range, with
   the cache append in the same launch (``decode_attn.py``)
+- multi-token attention over a KV cache on bf16 MFMA, split along the KV
+  range, with the append of the new rows (``append_attn.py``)
 """
 from __future__ import annotations
 

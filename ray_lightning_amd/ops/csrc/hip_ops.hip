@@ -1080,6 +1080,12 @@ torch::Tensor decode_attn_fwd_at_chunk(torch::Tensor qkv,
                                        torch::Tensor pos, int64_t max_pos,
                                        double scale, int64_t chunk);
 long decode_attn_chunk();
+// T new tokens per row over a KV cache: MFMA split-KV kernel with the
+// append of the T k/v rows — defined in append_attn.hip
+torch::Tensor append_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
+                              torch::Tensor v_cache, torch::Tensor pos,
+                              int64_t max_pos, double scale);
+long append_attn_chunk();
 // layout / instruction-semantics probes — defined in mfma_probe.hip
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor permlane_swap_probe();
@@ -1276,6 +1282,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode_attn_fwd at a chunk size of 64, 128 or 256 (measurement)");
   m.def("decode_attn_chunk", &decode_attn_chunk,
         "KV positions per workgroup of decode_attn_fwd");
+  m.def("append_attn_fwd", &append_attn_fwd,
+        "T-token attention over a KV cache (MFMA split-KV) + append",
+        pybind11::arg("qkv"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("pos"),
+        pybind11::arg("max_pos"), pybind11::arg("scale"));
+  m.def("append_attn_chunk", &append_attn_chunk,
+        "KV positions per workgroup of append_attn_fwd");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");

@@ -175,7 +175,7 @@ class KVCache:
         self.max_pos = int(max_len)
         self.prefilled = True
 
-    def advance(self) -> None:
-        """One token appended to every row."""
-        self.pos += 1
-        self.max_pos += 1
+    def advance(self, n: int = 1) -> None:
+        """``n`` tokens appended to every row."""
+        self.pos += n
+        self.max_pos += n
