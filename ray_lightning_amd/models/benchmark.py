@@ -117,7 +117,9 @@ class GPT2LM(LightningModule):
                  z_loss: float = 0.0, doc_eos_id: Optional[int] = None,
                  gen_max_new_tokens: int = 32, gen_temperature: float = 0.0,
                  gen_top_k: Optional[int] = None,
-                 gen_eos_id: Optional[int] = None):
+                 gen_eos_id: Optional[int] = None,
+                 gen_top_p: Optional[float] = None,
+                 gen_seed=None):
         super().__init__()
         self.save_hyperparameters()
         # predict_step: how GPT2.generate continues a batch of prompts
@@ -125,6 +127,8 @@ class GPT2LM(LightningModule):
         self.gen_temperature = gen_temperature
         self.gen_top_k = gen_top_k
         self.gen_eos_id = gen_eos_id
+        self.gen_top_p = gen_top_p
+        self.gen_seed = gen_seed
         # packed rows: when set, training_step derives document ids from
         # this EOS token and attention / positions stay within documents
         self.doc_eos_id = doc_eos_id
@@ -178,7 +182,8 @@ class GPT2LM(LightningModule):
         return self.model.generate(
             idx, self.gen_max_new_tokens, prompt_lens=prompt_lens,
             temperature=self.gen_temperature, top_k=self.gen_top_k,
-            eos_token_id=self.gen_eos_id)
+            eos_token_id=self.gen_eos_id, top_p=self.gen_top_p,
+            seed=self.gen_seed)
 
     def configure_optimizers(self):
         decay, no_decay = [], []

@@ -377,7 +377,8 @@ class GPT2(nn.Module):
                  pad_token_id: int = 0,
                  generator: Optional[torch.Generator] = None,
                  return_logits: bool = False,
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None,
+                 top_p: Optional[float] = None, seed=None):
         """Sample ``max_new_tokens`` tokens per row after the prompts.
 
         ``idx`` [B, P] holds the prompts, right-padded; ``prompt_lens``
@@ -392,6 +393,17 @@ class GPT2(nn.Module):
         by ``temperature``, cut to the ``top_k`` largest when given, and
         sampled with ``torch.multinomial`` on ``generator``. A row that
         has emitted ``eos_token_id`` emits ``pad_token_id`` from then on.
+
+        With ``seed`` or ``top_p`` given, every step's sampling, EOS
+        handling and write into the result is one ``sample_tokens`` call
+        (ops/sample.py: one HIP kernel on the GPU) on the LM head's
+        logits as they are. ``top_p`` in (0, 1] keeps the nucleus of the
+        ``top_k`` set. ``seed`` is an int (row ``b`` draws from the
+        Philox stream ``seed + b``) or a sequence of ``B`` ints; step
+        ``s`` of a row is counter ``s`` of its stream, so from equal
+        logits a row draws the same tokens alone as in any batch.
+        ``top_p`` without ``seed`` draws one seed from ``generator`` (or
+        torch's default) at the start of the call.
 
         One prefill forward over the prompts (padded up to a multiple of
         64 positions so the flash kernels take it; the LM head runs on
@@ -422,6 +434,21 @@ class GPT2(nn.Module):
             raise ValueError("max_new_tokens must be >= 0")
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError("prefill_chunk must be >= 1")
+        fused = seed is not None or top_p is not None
+        if top_p is not None and not 0 < top_p <= 1:
+            raise ValueError("top_p must be in (0, 1]")
+        if fused:
+            if seed is None:
+                seed = int(torch.randint(
+                    0, 2 ** 62, (1,), generator=generator,
+                    device=None if generator is None else generator.device))
+            row_seeds = [seed + b for b in range(B)] \
+                if isinstance(seed, int) else [int(s) for s in seed]
+            if len(row_seeds) != B:
+                raise ValueError(f"seed must be an int or {B} ints")
+            # into int64, as two's complement
+            row_seeds = [(s + 2 ** 63) % 2 ** 64 - 2 ** 63
+                         for s in row_seeds]
         if prompt_lens is None:
             lens = [P] * B
         else:
@@ -439,13 +466,15 @@ class GPT2(nn.Module):
         dev = idx.device
         lens_dev = torch.tensor(lens, dtype=torch.int64, device=dev)
         out = torch.full((B, P + max_new_tokens), pad_token_id,
-                         dtype=idx.dtype, device=dev)
+                         dtype=torch.int64 if fused else idx.dtype,
+                         device=dev)
         in_prompt = torch.arange(P, device=dev)[None, :] < lens_dev[:, None]
         out[:, :P] = torch.where(in_prompt, idx, out[:, :P])
         V = cfg.vocab_size
         all_logits = torch.zeros(B, max_new_tokens, V, dtype=torch.float32,
                                  device=dev) if return_logits else None
         if max_new_tokens == 0:
+            out = out.to(idx.dtype)
             return (out, all_logits) if return_logits else out
 
         was_training = self.training
@@ -475,28 +504,47 @@ class GPT2(nn.Module):
             else:
                 h = self._prefill_in_slices(prompt, prefill_chunk, cache,
                                             lens_dev, max_len, pad_token_id)
-            logits = self.lm_head(h).float()
+            logits = self.lm_head(h)
+            if not fused:
+                logits = logits.float()
 
             finished = torch.zeros(B, dtype=torch.bool, device=dev)
+            if fused:
+                from ..ops.sample import sample_tokens
+                seeds = torch.tensor(row_seeds, dtype=torch.int64,
+                                     device=dev)
+                col = lens_dev.clone()
             for step in range(max_new_tokens):
                 if return_logits:
                     all_logits[:, step] = logits
-                tok = self._sample(logits, temperature, top_k, generator)
-                if eos_token_id is not None:
-                    tok = torch.where(finished, tok.new_tensor(pad_token_id),
-                                      tok)
-                    finished = finished | (tok == eos_token_id)
-                out.scatter_(1, (lens_dev + step)[:, None],
-                             tok[:, None].to(out.dtype))
+                if fused:
+                    tok = sample_tokens(
+                        logits.contiguous(), seeds, step,
+                        temperature=temperature, top_k=top_k, top_p=top_p,
+                        finished=finished, eos=eos_token_id,
+                        pad=pad_token_id, out=out, col=col)
+                    col += 1
+                else:
+                    tok = self._sample(logits, temperature, top_k,
+                                       generator)
+                    if eos_token_id is not None:
+                        tok = torch.where(finished,
+                                          tok.new_tensor(pad_token_id), tok)
+                        finished = finished | (tok == eos_token_id)
+                    out.scatter_(1, (lens_dev + step)[:, None],
+                                 tok[:, None].to(out.dtype))
                 if step + 1 == max_new_tokens:
                     break
                 if (eos_token_id is not None and step % 16 == 15
                         and bool(finished.all())):
                     break
                 h = self._hidden(tok[:, None], None, cache)
-                logits = self.lm_head(h[:, 0]).float()
+                logits = self.lm_head(h[:, 0])
+                if not fused:
+                    logits = logits.float()
         finally:
             self.train(was_training)
+        out = out.to(idx.dtype)
         return (out, all_logits) if return_logits else out
 
 def document_ids(idx: torch.Tensor, eos_token_id: int) -> torch.Tensor:

@@ -20,6 +20,8 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
   the cache append in the same launch (``decode_attn.py``)
 - multi-token attention over a KV cache on bf16 MFMA, split along the KV
   range, with the append of the new rows (``append_attn.py``)
+- token sampling for generation: top-k, top-p, a Philox draw per row and
+  the EOS / output-write epilogue in one launch (``sample.py``)
 """
 from __future__ import annotations
 

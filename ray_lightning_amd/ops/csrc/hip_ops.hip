@@ -1086,6 +1086,16 @@ torch::Tensor append_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
                               int64_t max_pos, double scale);
 long append_attn_chunk();
+// top-k / top-p / Philox token sampling with the decode loop's EOS and
+// output-write epilogue, one launch — defined in sample.hip
+torch::Tensor sample_fwd(torch::Tensor logits, torch::Tensor seeds,
+                         int64_t step, double temperature,
+                         c10::optional<int64_t> top_k,
+                         c10::optional<double> top_p,
+                         c10::optional<torch::Tensor> finished, int64_t eos,
+                         int64_t pad, c10::optional<torch::Tensor> out,
+                         c10::optional<torch::Tensor> col);
+long sample_items_per_thread(torch::Tensor logits);
 // layout / instruction-semantics probes — defined in mfma_probe.hip
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor permlane_swap_probe();
@@ -1289,6 +1299,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("max_pos"), pybind11::arg("scale"));
   m.def("append_attn_chunk", &append_attn_chunk,
         "KV positions per workgroup of append_attn_fwd");
+  m.def("sample_fwd", &sample_fwd,
+        "top-k / top-p / Philox sampling + EOS and output-write epilogue",
+        pybind11::arg("logits"), pybind11::arg("seeds"),
+        pybind11::arg("step"), pybind11::arg("temperature"),
+        pybind11::arg("top_k"), pybind11::arg("top_p"),
+        pybind11::arg("finished"), pybind11::arg("eos"),
+        pybind11::arg("pad"), pybind11::arg("out"), pybind11::arg("col"));
+  m.def("sample_items_per_thread", &sample_items_per_thread,
+        "elements per thread sample_fwd holds for these logits (0: none)");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");
