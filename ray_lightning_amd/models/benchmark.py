@@ -119,7 +119,8 @@ class GPT2LM(LightningModule):
                  gen_top_k: Optional[int] = None,
                  gen_eos_id: Optional[int] = None,
                  gen_top_p: Optional[float] = None,
-                 gen_seed=None):
+                 gen_seed=None, *, gen_draft_tokens: int = 0,
+                 gen_draft_ngram: int = 3):
         super().__init__()
         self.save_hyperparameters()
         # predict_step: how GPT2.generate continues a batch of prompts
@@ -129,6 +130,8 @@ class GPT2LM(LightningModule):
         self.gen_eos_id = gen_eos_id
         self.gen_top_p = gen_top_p
         self.gen_seed = gen_seed
+        self.gen_draft_tokens = gen_draft_tokens
+        self.gen_draft_ngram = gen_draft_ngram
         # packed rows: when set, training_step derives document ids from
         # this EOS token and attention / positions stay within documents
         self.doc_eos_id = doc_eos_id
@@ -183,7 +186,8 @@ class GPT2LM(LightningModule):
             idx, self.gen_max_new_tokens, prompt_lens=prompt_lens,
             temperature=self.gen_temperature, top_k=self.gen_top_k,
             eos_token_id=self.gen_eos_id, top_p=self.gen_top_p,
-            seed=self.gen_seed)
+            seed=self.gen_seed, draft_tokens=self.gen_draft_tokens,
+            draft_ngram=self.gen_draft_ngram)
 
     def configure_optimizers(self):
         decay, no_decay = [], []

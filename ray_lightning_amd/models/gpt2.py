@@ -378,7 +378,9 @@ class GPT2(nn.Module):
                  generator: Optional[torch.Generator] = None,
                  return_logits: bool = False,
                  prefill_chunk: Optional[int] = None,
-                 top_p: Optional[float] = None, seed=None):
+                 top_p: Optional[float] = None, seed=None,
+                 draft_tokens: int = 0, draft_ngram: int = 3,
+                 return_stats: bool = False):
         """Sample ``max_new_tokens`` tokens per row after the prompts.
 
         ``idx`` [B, P] holds the prompts, right-padded; ``prompt_lens``
@@ -423,6 +425,24 @@ class GPT2(nn.Module):
         head still runs on the ``B`` rows at ``prompt_lens - 1`` only.
         The default (``None``) is the single prefill forward.
 
+        ``draft_tokens=T`` (1 to 15) is prompt-lookup speculative
+        decoding: every step drafts ``T`` tokens per row by looking the
+        row's last ``draft_ngram`` (1 to 8) tokens up in its own history,
+        runs one ``extend`` forward over ``[last token, T drafts]`` and
+        commits the accepted drafts plus one more token, all after the LM
+        head in one ``spec_step`` call (ops/spec_decode.py: one HIP kernel
+        on the GPU). Sampling is the seeded rule above with the number of
+        tokens the row has emitted as the counter, so from equal logits
+        the call returns what it returns with ``draft_tokens=0`` and the
+        same ``seed``; a seed is drawn as for ``top_p`` when none is
+        given. Three small integers per row (cache length, tokens
+        emitted, finished) are read back per step, for the cache's bound
+        and the end of the loop. Near the position limit
+        the drafts shorten, down to none. ``return_logits`` does not
+        combine with it. ``return_stats=True`` also returns ``{"forwards":
+        extend forwards run, "committed": tokens they committed over all
+        rows}`` (both 0 without drafts).
+
         Runs without gradients, in eval mode; the module's mode is put
         back afterwards."""
         from ..ops.decode_attn import KVCache, decode_attn_chunk
@@ -434,7 +454,16 @@ class GPT2(nn.Module):
             raise ValueError("max_new_tokens must be >= 0")
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError("prefill_chunk must be >= 1")
-        fused = seed is not None or top_p is not None
+        spec = draft_tokens != 0
+        if spec:
+            if not 1 <= draft_tokens <= 15:
+                raise ValueError("draft_tokens must be in [0, 15]")
+            if not 1 <= draft_ngram <= 8:
+                raise ValueError("draft_ngram must be in [1, 8]")
+            if return_logits:
+                raise ValueError(
+                    "draft_tokens and return_logits do not combine")
+        fused = spec or seed is not None or top_p is not None
         if top_p is not None and not 0 < top_p <= 1:
             raise ValueError("top_p must be in (0, 1]")
         if fused:
@@ -473,8 +502,12 @@ class GPT2(nn.Module):
         V = cfg.vocab_size
         all_logits = torch.zeros(B, max_new_tokens, V, dtype=torch.float32,
                                  device=dev) if return_logits else None
+        stats = {"forwards": 0, "committed": 0}
         if max_new_tokens == 0:
             out = out.to(idx.dtype)
+            if return_stats:
+                return (out, all_logits, stats) if return_logits \
+                    else (out, stats)
             return (out, all_logits) if return_logits else out
 
         was_training = self.training
@@ -514,7 +547,13 @@ class GPT2(nn.Module):
                 seeds = torch.tensor(row_seeds, dtype=torch.int64,
                                      device=dev)
                 col = lens_dev.clone()
-            for step in range(max_new_tokens):
+            if spec:
+                self._generate_drafted(
+                    logits, cache, seeds, col, finished, out,
+                    max_new_tokens, draft_tokens, draft_ngram, stats,
+                    dict(temperature=temperature, top_k=top_k, top_p=top_p,
+                         eos=eos_token_id, pad=pad_token_id))
+            for step in range(0 if spec else max_new_tokens):
                 if return_logits:
                     all_logits[:, step] = logits
                 if fused:
@@ -545,7 +584,47 @@ class GPT2(nn.Module):
         finally:
             self.train(was_training)
         out = out.to(idx.dtype)
+        if return_stats:
+            return (out, all_logits, stats) if return_logits \
+                else (out, stats)
         return (out, all_logits) if return_logits else out
+
+    def _generate_drafted(self, logits, cache, seeds, col, finished, out,
+                          limit, T, ngram, stats, kw):
+        """The loop of ``generate(draft_tokens=T)`` after the prefill.
+        ``logits`` [B, V] are the prefill's; ``col`` [B] is where each
+        row's next token goes in ``out``. After every ``spec_step`` a
+        row's cache holds all its tokens but the last one committed:
+        ``pos == col - 1``. The first call has ``T1 = 1`` and follows no
+        ``advance``; its ``pos += n - T1`` adds 0, since ``limit >= 1``
+        gives ``n = 1``, and the prefill left ``pos = col``."""
+        from ..ops.spec_decode import spec_step
+        B, dev = logits.shape[0], logits.device
+        emitted = torch.zeros(B, dtype=torch.int64, device=dev)
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
+        # max_new_tokens == 1 runs without a cache
+        pos = cache.pos if cache is not None else \
+            torch.zeros(B, dtype=torch.int32, device=dev)
+        room = 0 if cache is None else \
+            min(cache.Tmax, self.cfg.n_positions)
+        state = dict(finished=finished, out=out, col=col, pos=pos, done=done,
+                     ngram=ngram, **kw)
+        _, _, next_idx = spec_step(
+            logits[:, None].contiguous(), out.new_empty(B, 0), seeds,
+            emitted, limit, next_T=T if limit > 1 else 0, **state)
+        while True:
+            host = torch.stack((pos.to(torch.int64), emitted,
+                                finished.to(torch.int64))).tolist()
+            stats["committed"] = sum(host[1]) - B
+            if all(e == limit or f for e, f in zip(host[1], host[2])):
+                return
+            cache.set_max_pos(max(host[0]))
+            Tn = min(T, room - cache.max_pos - 1)
+            h = self._hidden(next_idx[:, :1 + Tn], None, cache, extend=True)
+            _, _, next_idx = spec_step(
+                self.lm_head(h), next_idx[:, 1:1 + Tn], seeds, emitted,
+                limit, next_T=T, **state)
+            stats["forwards"] += 1
 
 def document_ids(idx: torch.Tensor, eos_token_id: int) -> torch.Tensor:
     """Document ids [B, T] of a packed token stream: the number of EOS

@@ -1096,6 +1096,17 @@ torch::Tensor sample_fwd(torch::Tensor logits, torch::Tensor seeds,
                          int64_t pad, c10::optional<torch::Tensor> out,
                          c10::optional<torch::Tensor> col);
 long sample_items_per_thread(torch::Tensor logits);
+// one step of prompt-lookup speculative decoding after the LM head:
+// sampling at T + 1 positions, acceptance, commit and the next draft in
+// one launch — defined in spec_decode.hip
+std::vector<torch::Tensor> spec_step(
+    torch::Tensor logits, torch::Tensor draft, torch::Tensor seeds,
+    torch::Tensor emitted, int64_t limit, double temperature,
+    c10::optional<int64_t> top_k, c10::optional<double> top_p,
+    torch::Tensor finished, int64_t eos, int64_t pad, torch::Tensor out,
+    torch::Tensor col, torch::Tensor pos, torch::Tensor done, int64_t ngram,
+    int64_t next_T);
+long spec_items_per_thread(torch::Tensor logits);
 // layout / instruction-semantics probes — defined in mfma_probe.hip
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor permlane_swap_probe();
@@ -1308,6 +1319,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("pad"), pybind11::arg("out"), pybind11::arg("col"));
   m.def("sample_items_per_thread", &sample_items_per_thread,
         "elements per thread sample_fwd holds for these logits (0: none)");
+  m.def("spec_step", &spec_step,
+        "speculative step: sample T + 1 positions, accept, commit, draft",
+        pybind11::arg("logits"), pybind11::arg("draft"),
+        pybind11::arg("seeds"), pybind11::arg("emitted"),
+        pybind11::arg("limit"), pybind11::arg("temperature"),
+        pybind11::arg("top_k"), pybind11::arg("top_p"),
+        pybind11::arg("finished"), pybind11::arg("eos"),
+        pybind11::arg("pad"), pybind11::arg("out"), pybind11::arg("col"),
+        pybind11::arg("pos"), pybind11::arg("done"), pybind11::arg("ngram"),
+        pybind11::arg("next_T"));
+  m.def("spec_items_per_thread", &spec_items_per_thread,
+        "elements per thread spec_step holds for these logits (0: none)");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("flash_attn_fwd_v4", &flash_attn_fwd_v4,
         "32x32x16 MFMA flash attention fwd (v4)");

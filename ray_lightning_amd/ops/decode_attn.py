@@ -175,6 +175,11 @@ class KVCache:
         self.max_pos = int(max_len)
         self.prefilled = True
 
+    def set_max_pos(self, max_pos: int) -> None:
+        """The host's bound on ``pos`` after the device changed ``pos``
+        itself (ops/spec_decode.py): what the caller read back."""
+        self.max_pos = int(max_pos)
+
     def advance(self, n: int = 1) -> None:
         """``n`` tokens appended to every row."""
         self.pos += n

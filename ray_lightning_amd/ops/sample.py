@@ -83,7 +83,9 @@ def _kernel_shape(logits: torch.Tensor) -> bool:
 
 
 def _twin(logits, seeds, step, temperature, top_k, top_p):
+    """``step`` is one int for all rows or a list of ``B`` ints."""
     B, V = logits.shape
+    steps = step if isinstance(step, (list, tuple)) else [step] * B
     dev = logits.device
     l = torch.nan_to_num(logits.float(), nan=-torch.inf, posinf=_FLT_MAX,
                          neginf=-torch.inf)
@@ -117,7 +119,8 @@ def _twin(logits, seeds, step, temperature, top_k, top_p):
         m = torch.where(kept, m, zero[:, None])
     cum = m.cumsum(1)
     MN = cum[:, -1]
-    x = torch.tensor([philox_word0(s, step) for s in seeds.tolist()],
+    x = torch.tensor([philox_word0(s, st)
+                      for s, st in zip(seeds.tolist(), steps)],
                      dtype=torch.int64, device=dev)
     # floor(MN * x / 2^32) without leaving int64: MN = hi * 2^28 + lo
     hi, lo = MN >> 28, MN & ((1 << 28) - 1)
