@@ -27,7 +27,11 @@ cache=...)`` is the same machinery one call at a time, and
 ``forward(idx, cache=..., extend=True)`` appends ``T`` tokens per row to
 a filled cache through the MFMA append kernel (ops/append_attn.py): the
 next turn of a conversation, a slice of a chunked prefill
-(``generate(prefill_chunk=)``), drafted tokens to verify.
+(``generate(prefill_chunk=)``), drafted tokens to verify. With
+``RLA_SKINNY_LINEAR`` on (docs/CONFIG.md), a decode step of a bf16 model
+with at most 64 rows runs every block as one ``decode_layer`` call and
+the final LayerNorm with the LM head as one ``skinny_linear`` call
+(ops/skinny_linear.py).
 """
 from __future__ import annotations
 
@@ -231,6 +235,9 @@ class GPT2(nn.Module):
         token attends them, and their cache slots lie at or above the
         row's new length: they are overwritten before they are ever
         attended."""
+        if targets is None and doc_ids is None and \
+                self._fused_decode(idx, cache, extend):
+            return self._decode_logits(idx, cache)[:, None], None
         x = self._hidden(idx, doc_ids, cache, extend)
         if targets is not None:
             # chunked LM-head + CE: never materializes the [B*T, V]
@@ -323,6 +330,55 @@ class GPT2(nn.Module):
                 torch.full((B,), T, dtype=torch.int32, device=idx.device),
                 T)
         return h  # = ln_f(x)
+
+    def _fused_decode(self, idx, cache, extend=False) -> bool:
+        """Whether this call is a decode step that runs through
+        ``decode_layer`` (ops/skinny_linear.py): one token per row over a
+        filled cache, at most 64 rows, a bf16 model in eval mode, the
+        gate on. On the GPU also only where the kernels take the model's
+        linears (fp32 LayerNorm parameters, widths in 32s, the extension
+        loaded): there the torch twin, which widens every weight matrix
+        per call, would be slower than the composed path."""
+        if cache is None or not cache.prefilled or extend or self.training \
+                or len(self.h) == 0:
+            return False
+        if idx.dim() != 2 or idx.shape[1] != 1 or not 1 <= idx.shape[0] <= 64:
+            return False
+        from ..ops.skinny_linear import kernel_enabled, kernel_serves
+        w = self.wte.weight
+        if w.dtype != torch.bfloat16 or not kernel_enabled():
+            return False
+        b0 = self.h[0]
+        return not w.is_cuda or (
+            kernel_serves(b0.attn.c_attn.weight, b0.ln_1.weight)
+            and kernel_serves(b0.mlp.c_fc.weight, b0.ln_2.weight)
+            and kernel_serves(b0.mlp.c_proj.weight)
+            and kernel_serves(self.lm_head.weight, self.ln_f.weight))
+
+    def _decode_logits(self, idx, cache):
+        """The logits [B, V] of one decode step over ``idx`` [B, 1]. On
+        the fused path every block is one ``decode_layer`` call and the
+        last residual add, ``ln_f`` and the LM head are one
+        ``skinny_linear`` call; otherwise ``_hidden`` and the LM head."""
+        if not self._fused_decode(idx, cache):
+            return self.lm_head(self._hidden(idx, None, cache)[:, 0])
+        from ..ops.skinny_linear import decode_layer, skinny_linear
+        if cache.max_pos + 1 > cache.Tmax:
+            raise ValueError(
+                f"the cache holds {cache.Tmax} positions per row")
+        x = self.wte(idx[:, 0]) + self.wpe(cache.pos.to(torch.int64))
+        res = None
+        for i, block in enumerate(self.h):
+            res, x = decode_layer(
+                x, res, block.ln_1, block.attn.c_attn, cache.k[i],
+                cache.v[i], cache.pos, cache.max_pos, block.attn.c_proj,
+                block.ln_2, block.mlp.c_fc, block.mlp.c_proj)
+        logits, _ = skinny_linear(
+            x, self.lm_head.weight, None, residual=res,
+            ln_weight=self.ln_f.weight, ln_bias=self.ln_f.bias,
+            eps=self.ln_f.eps)
+        cache.advance()
+        return logits
 
     @staticmethod
     def _sample(logits, temperature, top_k, generator):
@@ -577,8 +633,7 @@ class GPT2(nn.Module):
                 if (eos_token_id is not None and step % 16 == 15
                         and bool(finished.all())):
                     break
-                h = self._hidden(tok[:, None], None, cache)
-                logits = self.lm_head(h[:, 0])
+                logits = self._decode_logits(tok[:, None], cache)
                 if not fused:
                     logits = logits.float()
         finally:

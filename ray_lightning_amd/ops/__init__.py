@@ -22,6 +22,9 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
   range, with the append of the new rows (``append_attn.py``)
 - token sampling for generation: top-k, top-p, a Philox draw per row and
   the EOS / output-write epilogue in one launch (``sample.py``)
+- linear layers of a decode step (at most 64 rows) as an MFMA weight
+  stream with residual add, LayerNorm, bias and GELU fused, and a GPT-2
+  block of a decode step from one host call (``skinny_linear.py``)
 """
 from __future__ import annotations
 

@@ -1086,6 +1086,29 @@ torch::Tensor append_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
                               int64_t max_pos, double scale);
 long append_attn_chunk();
+// linear layers of a decode step (M <= 64 rows): MFMA weight stream with
+// LayerNorm / residual add in the prologue and bias / GELU in the epilogue,
+// and one GPT-2 block of a decode step from one call — defined in
+// skinny_linear.hip
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> skinny_linear_fwd(
+    torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> bias,
+    c10::optional<torch::Tensor> residual,
+    c10::optional<torch::Tensor> ln_weight,
+    c10::optional<torch::Tensor> ln_bias, double eps, bool gelu);
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> skinny_linear_fwd_at(
+    torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> bias,
+    c10::optional<torch::Tensor> residual,
+    c10::optional<torch::Tensor> ln_weight,
+    c10::optional<torch::Tensor> ln_bias, double eps, bool gelu,
+    int64_t waves, int64_t row_tiles);
+std::tuple<torch::Tensor, torch::Tensor> decode_layer_fwd(
+    torch::Tensor x, c10::optional<torch::Tensor> residual,
+    torch::Tensor ln1_w, torch::Tensor ln1_b, torch::Tensor attn_w,
+    torch::Tensor attn_b, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor pos, int64_t max_pos, double scale, torch::Tensor proj_w,
+    torch::Tensor proj_b, torch::Tensor ln2_w, torch::Tensor ln2_b,
+    torch::Tensor fc_w, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
+    torch::Tensor mlp_proj_b, double eps);
 // top-k / top-p / Philox token sampling with the decode loop's EOS and
 // output-write epilogue, one launch — defined in sample.hip
 torch::Tensor sample_fwd(torch::Tensor logits, torch::Tensor seeds,
@@ -1310,6 +1333,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("max_pos"), pybind11::arg("scale"));
   m.def("append_attn_chunk", &append_attn_chunk,
         "KV positions per workgroup of append_attn_fwd");
+  m.def("skinny_linear_fwd", &skinny_linear_fwd,
+        "y = act(LN(x + residual) @ W^T + bias) for M <= 64 rows; returns "
+        "(y, x_new or None)",
+        pybind11::arg("x"), pybind11::arg("weight"), pybind11::arg("bias"),
+        pybind11::arg("residual"), pybind11::arg("ln_weight"),
+        pybind11::arg("ln_bias"), pybind11::arg("eps"),
+        pybind11::arg("gelu"));
+  m.def("skinny_linear_fwd_at", &skinny_linear_fwd_at,
+        "skinny_linear_fwd at (waves, row_tiles) of (4, 1), (8, 1) or "
+        "(8, 2) (measurement)");
+  m.def("decode_layer_fwd", &decode_layer_fwd,
+        "one GPT-2 block of a decode step: returns (x_mid, mlp_out)");
   m.def("sample_fwd", &sample_fwd,
         "top-k / top-p / Philox sampling + EOS and output-write epilogue",
         pybind11::arg("logits"), pybind11::arg("seeds"),

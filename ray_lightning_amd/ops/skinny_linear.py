@@ -1,0 +1,195 @@
+"""Linear layers of a decode step: at most 64 rows against a weight matrix.
+
+``skinny_linear(x, weight, bias, residual=, ln_weight=, ln_bias=, eps=,
+gelu=)`` computes ``y = act(h @ weight.T + bias)`` for ``x`` [M, K] and
+``weight`` [N, K] as ``nn.Linear`` stores it, where ``h`` is
+
+- ``x`` itself,
+- ``LN(x)`` when ``ln_weight`` / ``ln_bias`` are given, or
+- ``LN(x_new)`` with ``x_new = x + residual`` when ``residual`` is given
+  too (then the call returns ``(y, x_new)``: ``x_new`` is the residual
+  stream of a pre-norm block),
+
+and ``act`` is the identity or, with ``gelu=True``, tanh-GELU. Rounding
+points, in the operands' dtype: ``x_new``, ``h``, and ``y`` once after
+bias and GELU; LayerNorm statistics, the accumulation and GELU are fp32.
+
+``decode_layer(...)`` is one GPT-2 block of a decode step built from it:
+[add + LN1 + c_attn], ``decode_attention`` over the KV cache (with the
+append), [c_proj], [add + LN2 + c_fc + GELU], [c_proj].
+
+On the GPU, for bf16 with ``M <= 64``, ``K % 32 == 0`` and fp32 LayerNorm
+parameters, both are the HIP code of csrc/skinny_linear.hip: an MFMA
+kernel that streams the weights once, with the pointwise neighbours in
+its prologue and epilogue, and for ``decode_layer`` one host call that
+enqueues the block's six kernels (docs/DESIGN.md §18,
+profiles/skinny_linear.md). With ``RLA_DECODE_ATTN=0`` the block is
+composed here instead, from the linear kernels and ``decode_attention``'s
+twin. Whether that is the default is
+``_SKINNY_DEFAULT`` below; ``RLA_SKINNY_LINEAR=1`` / ``=0`` forces it on
+/ off. Everything else (CPU, other dtypes, more rows, other ``K``, the
+gate off) runs the torch twin with the same semantics.
+"""
+from __future__ import annotations
+
+import math
+import os
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import _load_ext
+from .decode_attn import _kernel_enabled as _attn_kernel_enabled
+from .decode_attn import decode_attention
+
+# Off although the measurement in profiles/skinny_linear.md meets the rule
+# set for it (GPT-2-XL's decode step faster at both B = 8 and B = 1 by more
+# than the runs' spread): the one-call-per-block path reaches decode
+# attention from C++, past the Python entry at which the generation tests
+# count its calls, and M = 64 loses per call. The profile has both.
+_SKINNY_DEFAULT = False
+
+MAX_ROWS = 64
+
+
+def kernel_enabled() -> bool:
+    """The gate: ``RLA_SKINNY_LINEAR`` when set, else the default."""
+    env = os.environ.get("RLA_SKINNY_LINEAR")
+    if env is None:
+        return _SKINNY_DEFAULT
+    return env == "1"
+
+
+def kernel_serves(weight, ln_weight=None) -> bool:
+    """Whether the kernel takes this ``weight`` [N, K] (and LayerNorm
+    parameter) for up to ``MAX_ROWS`` bf16 rows; the gate is apart."""
+    return (weight.is_cuda and weight.dtype == torch.bfloat16
+            and weight.dim() == 2 and weight.shape[1] % 32 == 0
+            and weight.shape[1] >= 32
+            and (ln_weight is None or ln_weight.dtype == torch.float32)
+            and _load_ext() is not None)
+
+
+def _kernel_shape(x, weight, ln_weight) -> bool:
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2
+            and x.shape[0] <= MAX_ROWS and kernel_serves(weight, ln_weight))
+
+
+def _ext_with(symbol: str):
+    ext = _load_ext()
+    if not hasattr(ext, symbol):
+        raise RuntimeError(
+            f"_hip_ops has no {symbol}: rebuild with "
+            "`python -m ray_lightning_amd.ops.build`")
+    return ext
+
+
+def _twin(x, weight, bias, residual, ln_weight, ln_bias, eps, gelu):
+    dt = x.dtype
+    wide = torch.promote_types(dt, torch.float32)
+    x_new = None
+    if residual is not None:
+        x_new = (x.to(wide) + residual.to(wide)).to(dt)
+        x = x_new
+    if ln_weight is not None:
+        x = F.layer_norm(x.to(wide), (x.shape[-1],), ln_weight.to(wide),
+                         ln_bias.to(wide), eps).to(dt)
+    y = x.to(wide) @ weight.to(wide).t()
+    if bias is not None:
+        y = y + bias.to(wide)
+    if gelu:
+        y = F.gelu(y, approximate="tanh")
+    return y.to(dt), x_new
+
+
+def _check(x, weight, bias, residual, ln_weight, ln_bias):
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(
+            f"x must be [M, K] and weight [N, K], got {list(x.shape)} and "
+            f"{list(weight.shape)}")
+    if weight.shape[0] < 1:
+        raise ValueError("weight has no rows")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(
+            f"bias must be [N] = [{weight.shape[0]}], got "
+            f"{list(bias.shape)}")
+    if (ln_weight is None) != (ln_bias is None):
+        raise ValueError("ln_weight and ln_bias come together or not at all")
+    if ln_weight is not None:
+        for p in (ln_weight, ln_bias):
+            if tuple(p.shape) != (x.shape[1],):
+                raise ValueError(
+                    f"ln_weight and ln_bias must be [K] = [{x.shape[1]}]")
+    if residual is not None:
+        if ln_weight is None:
+            raise ValueError(
+                "a residual is only taken together with LayerNorm")
+        if residual.shape != x.shape or residual.dtype != x.dtype:
+            raise ValueError("residual must have x's shape and dtype")
+
+
+def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
+                  bias: Optional[torch.Tensor] = None, *,
+                  residual: Optional[torch.Tensor] = None,
+                  ln_weight: Optional[torch.Tensor] = None,
+                  ln_bias: Optional[torch.Tensor] = None,
+                  eps: float = 1e-5, gelu: bool = False):
+    """``act(LN(x + residual) @ weight.T + bias)`` (module docstring).
+    Returns ``y`` [M, N], or ``(y, x_new)`` when ``residual`` is given."""
+    _check(x, weight, bias, residual, ln_weight, ln_bias)
+    if _kernel_shape(x, weight, ln_weight) and kernel_enabled():
+        # the one checked host path: every other operand check is there
+        y, x_new = _ext_with("skinny_linear_fwd").skinny_linear_fwd(
+            x, weight, bias, residual, ln_weight, ln_bias, float(eps),
+            bool(gelu))
+    else:
+        y, x_new = _twin(x, weight, bias, residual, ln_weight, ln_bias, eps,
+                         gelu)
+    return y if residual is None else (y, x_new)
+
+
+def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
+                 ln1, c_attn, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                 pos: torch.Tensor, max_pos: int, attn_proj, ln2, c_fc,
+                 mlp_proj):
+    """One pre-norm GPT-2 block of a decode step. ``x`` [B, C] is the
+    previous block's MLP output and ``residual`` the stream it is added
+    to; for the first block ``x`` is the stream and ``residual`` is
+    ``None``. ``ln1`` / ``ln2`` are the block's LayerNorm modules and
+    ``c_attn`` / ``attn_proj`` / ``c_fc`` / ``mlp_proj`` its ``nn.Linear``
+    modules; the caches [B, H, Tmax, hs], ``pos`` and ``max_pos`` are
+    ``decode_attention``'s. Returns ``(x_mid, mlp_out)``: the stream after
+    the attention sublayer and the MLP's output, which the next block (or
+    the final LayerNorm) takes as ``(residual, x)``."""
+    B, C = x.shape
+    hs = k_cache.shape[-1]
+    if ln1.eps != ln2.eps:
+        raise ValueError("ln1 and ln2 differ in eps")
+    # the one call reaches decode attention's kernel from C++, so that
+    # kernel's own gate (RLA_DECODE_ATTN) has to be on as well
+    if (_kernel_shape(x, c_attn.weight, ln1.weight) and kernel_enabled()
+            and _attn_kernel_enabled()
+            and hs == 64 and k_cache.dtype == torch.bfloat16
+            and c_fc.weight.shape[0] % 32 == 0
+            and ln2.weight.dtype == torch.float32
+            and all(m.bias is not None
+                    for m in (c_attn, attn_proj, c_fc, mlp_proj))):
+        return _ext_with("decode_layer_fwd").decode_layer_fwd(
+            x, residual, ln1.weight, ln1.bias, c_attn.weight, c_attn.bias,
+            k_cache, v_cache, pos, int(max_pos), 1.0 / math.sqrt(hs),
+            attn_proj.weight, attn_proj.bias, ln2.weight, ln2.bias,
+            c_fc.weight, c_fc.bias, mlp_proj.weight, mlp_proj.bias,
+            float(ln1.eps))
+    ln = dict(ln_weight=ln1.weight, ln_bias=ln1.bias, eps=ln1.eps)
+    if residual is None:
+        qkv, x1 = skinny_linear(x, c_attn.weight, c_attn.bias, **ln), x
+    else:
+        qkv, x1 = skinny_linear(x, c_attn.weight, c_attn.bias,
+                                residual=residual, **ln)
+    att = decode_attention(qkv, k_cache, v_cache, pos, max_pos)
+    att = skinny_linear(att, attn_proj.weight, attn_proj.bias)
+    hid, x_mid = skinny_linear(att, c_fc.weight, c_fc.bias, residual=x1,
+                               ln_weight=ln2.weight, ln_bias=ln2.bias,
+                               eps=ln2.eps, gelu=True)
+    return x_mid, skinny_linear(hid, mlp_proj.weight, mlp_proj.bias)
