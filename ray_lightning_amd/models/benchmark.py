@@ -120,7 +120,7 @@ class GPT2LM(LightningModule):
                  gen_eos_id: Optional[int] = None,
                  gen_top_p: Optional[float] = None,
                  gen_seed=None, *, gen_draft_tokens: int = 0,
-                 gen_draft_ngram: int = 3):
+                 gen_draft_ngram: int = 3, gen_fp8_weights: bool = False):
         super().__init__()
         self.save_hyperparameters()
         # predict_step: how GPT2.generate continues a batch of prompts
@@ -132,6 +132,10 @@ class GPT2LM(LightningModule):
         self.gen_seed = gen_seed
         self.gen_draft_tokens = gen_draft_tokens
         self.gen_draft_ngram = gen_draft_ngram
+        # weight-only fp8 for decode steps (GPT2.quantize_weights_fp8),
+        # applied once, before the first predict_step
+        self.gen_fp8_weights = gen_fp8_weights
+        self._fp8_quantized = False
         # packed rows: when set, training_step derives document ids from
         # this EOS token and attention / positions stay within documents
         self.doc_eos_id = doc_eos_id
@@ -182,6 +186,9 @@ class GPT2LM(LightningModule):
             prompt_lens = torch.as_tensor(prompt_lens).cpu()
         else:
             idx = batch
+        if self.gen_fp8_weights and not self._fp8_quantized:
+            self.model.eval().quantize_weights_fp8()
+            self._fp8_quantized = True
         return self.model.generate(
             idx, self.gen_max_new_tokens, prompt_lens=prompt_lens,
             temperature=self.gen_temperature, top_k=self.gen_top_k,

@@ -31,7 +31,8 @@ next turn of a conversation, a slice of a chunked prefill
 ``RLA_SKINNY_LINEAR`` on (docs/CONFIG.md), a decode step of a bf16 model
 with at most 64 rows runs every block as one ``decode_layer`` call and
 the final LayerNorm with the LM head as one ``skinny_linear`` call
-(ops/skinny_linear.py).
+(ops/skinny_linear.py). After ``GPT2.quantize_weights_fp8()`` those decode
+steps stream the blocks' linear weights as fp8 (``RLA_SKINNY_FP8``).
 """
 from __future__ import annotations
 
@@ -330,6 +331,31 @@ class GPT2(nn.Module):
                 torch.full((B,), T, dtype=torch.int32, device=idx.device),
                 T)
         return h  # = ln_f(x)
+
+    @torch.no_grad()
+    def quantize_weights_fp8(self) -> "GPT2":
+        """Weight-only fp8 for the four linears of every block, on a bf16
+        model in eval mode: each bf16 ``weight`` is overwritten with its
+        dequantized e4m3 values (exact in bf16), and the codes and row
+        scales are kept next to it as non-persistent buffers
+        ``weight_fp8`` / ``weight_scale``, so state dicts do not change.
+        ``decode_layer`` streams the fp8 copy; the bf16 copy stays and
+        serves prefill, ``extend`` and every other path, which compute the
+        same function, so the blocks' weight memory grows by half. The
+        embeddings and the LM head stay bf16. Call it again after the
+        weights change; returns ``self``."""
+        from ..ops.skinny_linear import dequantize_weight, quantize_weight
+        if self.training or self.wte.weight.dtype != torch.bfloat16:
+            raise RuntimeError(
+                "quantize_weights_fp8 takes a bf16 model in eval mode")
+        for block in self.h:
+            for lin in (block.attn.c_attn, block.attn.c_proj,
+                        block.mlp.c_fc, block.mlp.c_proj):
+                q, scale = quantize_weight(lin.weight)
+                lin.weight.copy_(dequantize_weight(q, scale))
+                lin.register_buffer("weight_fp8", q, persistent=False)
+                lin.register_buffer("weight_scale", scale, persistent=False)
+        return self
 
     def _fused_decode(self, idx, cache, extend=False) -> bool:
         """Whether this call is a decode step that runs through

@@ -1094,7 +1094,8 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> skinny_linear_fwd(
     torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> bias,
     c10::optional<torch::Tensor> residual,
     c10::optional<torch::Tensor> ln_weight,
-    c10::optional<torch::Tensor> ln_bias, double eps, bool gelu);
+    c10::optional<torch::Tensor> ln_bias, double eps, bool gelu,
+    c10::optional<torch::Tensor> weight_scale);
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> skinny_linear_fwd_at(
     torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> bias,
     c10::optional<torch::Tensor> residual,
@@ -1109,6 +1110,23 @@ std::tuple<torch::Tensor, torch::Tensor> decode_layer_fwd(
     torch::Tensor proj_b, torch::Tensor ln2_w, torch::Tensor ln2_b,
     torch::Tensor fc_w, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
     torch::Tensor mlp_proj_b, double eps);
+// the same with float8_e4m3fn weights [N, K] and fp32 row scales [N]
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
+skinny_linear_fp8_fwd_at(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor weight_scale,
+    c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual,
+    c10::optional<torch::Tensor> ln_weight,
+    c10::optional<torch::Tensor> ln_bias, double eps, bool gelu,
+    int64_t row_tiles, bool wide, int64_t uk);
+std::tuple<torch::Tensor, torch::Tensor> decode_layer_fp8_fwd(
+    torch::Tensor x, c10::optional<torch::Tensor> residual,
+    torch::Tensor ln1_w, torch::Tensor ln1_b, torch::Tensor attn_w,
+    torch::Tensor attn_s, torch::Tensor attn_b, torch::Tensor k_cache,
+    torch::Tensor v_cache, torch::Tensor pos, int64_t max_pos, double scale,
+    torch::Tensor proj_w, torch::Tensor proj_s, torch::Tensor proj_b,
+    torch::Tensor ln2_w, torch::Tensor ln2_b, torch::Tensor fc_w,
+    torch::Tensor fc_s, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
+    torch::Tensor mlp_proj_s, torch::Tensor mlp_proj_b, double eps);
 // top-k / top-p / Philox token sampling with the decode loop's EOS and
 // output-write epilogue, one launch — defined in sample.hip
 torch::Tensor sample_fwd(torch::Tensor logits, torch::Tensor seeds,
@@ -1339,12 +1357,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x"), pybind11::arg("weight"), pybind11::arg("bias"),
         pybind11::arg("residual"), pybind11::arg("ln_weight"),
         pybind11::arg("ln_bias"), pybind11::arg("eps"),
-        pybind11::arg("gelu"));
+        pybind11::arg("gelu"),
+        pybind11::arg("weight_scale") = c10::optional<torch::Tensor>());
   m.def("skinny_linear_fwd_at", &skinny_linear_fwd_at,
         "skinny_linear_fwd at (waves, row_tiles) of (4, 1), (8, 1) or "
         "(8, 2) (measurement)");
   m.def("decode_layer_fwd", &decode_layer_fwd,
         "one GPT-2 block of a decode step: returns (x_mid, mlp_out)");
+  m.def("skinny_linear_fp8_fwd_at", &skinny_linear_fp8_fwd_at,
+        "skinny_linear_fwd with fp8 weights at (row_tiles, wide, uk) "
+        "(measurement)");
+  m.def("decode_layer_fp8_fwd", &decode_layer_fp8_fwd,
+        "decode_layer_fwd with float8_e4m3fn weights, each followed by its "
+        "fp32 row scales");
   m.def("sample_fwd", &sample_fwd,
         "top-k / top-p / Philox sampling + EOS and output-write epilogue",
         pybind11::arg("logits"), pybind11::arg("seeds"),

@@ -29,6 +29,18 @@ twin. Whether that is the default is
 ``_SKINNY_DEFAULT`` below; ``RLA_SKINNY_LINEAR=1`` / ``=0`` forces it on
 / off. Everything else (CPU, other dtypes, more rows, other ``K``, the
 gate off) runs the torch twin with the same semantics.
+
+fp8 weights. ``quantize_weight(weight)`` gives ``(q, scale)``: OCP
+``float8_e4m3fn`` codes [N, K] and one fp32 power-of-two scale per row,
+``scale[n] = 2^ceil(log2(absmax[n] / 448))``. ``skinny_linear(x, q, ...,
+weight_scale=scale)`` then streams the bytes and converts them to bf16 in
+registers (the fp8 kernels of csrc/skinny_linear.hip, docs/DESIGN.md §19,
+profiles/skinny_linear_fp8.md). ``q * scale`` is exact in bf16, so the
+same function is ``skinny_linear`` on the dequantized bf16 weight, which
+is what the twin computes. ``decode_layer`` takes the fp8 kernels when its
+four ``nn.Linear`` modules carry ``weight_fp8`` / ``weight_scale`` buffers
+(``GPT2.quantize_weights_fp8``) and ``RLA_SKINNY_FP8`` allows it
+(``_FP8_DEFAULT`` below when unset, ``1`` / ``0`` forces it).
 """
 from __future__ import annotations
 
@@ -50,7 +62,15 @@ from .decode_attn import decode_attention
 # count its calls, and M = 64 loses per call. The profile has both.
 _SKINNY_DEFAULT = False
 
+# Once a model is quantized, the fp8 kernels are the route: by the rule set
+# before the run, GPT-2-XL's decode step is faster with them than with the
+# bf16 kernels at both B = 8 and B = 1 by more than the runs' spread
+# (profiles/skinny_linear_fp8.md).
+_FP8_DEFAULT = True
+
 MAX_ROWS = 64
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
 
 
 def kernel_enabled() -> bool:
@@ -61,10 +81,44 @@ def kernel_enabled() -> bool:
     return env == "1"
 
 
+def fp8_enabled() -> bool:
+    """Whether quantized linears run the fp8 kernels: ``RLA_SKINNY_FP8``
+    when set, else the default."""
+    env = os.environ.get("RLA_SKINNY_FP8")
+    if env is None:
+        return _FP8_DEFAULT
+    return env != "0"
+
+
+def quantize_weight(weight: torch.Tensor):
+    """``(q, scale)`` for ``weight`` [N, K]: ``q`` float8_e4m3fn [N, K] and
+    ``scale`` fp32 [N], the smallest power of two with
+    ``absmax[n] / scale[n] <= 448`` (1 for an all-zero row).
+    ``q.float() * scale[:, None]`` is exact in bf16, and quantizing it
+    again gives the same values."""
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be [N, K], got {list(weight.shape)}")
+    w = weight.detach().float()
+    # frexp: absmax / 448 = m * 2^e with m in [0.5, 1), so ceil(log2) is e,
+    # or e - 1 at m = 0.5; exact, where log2 would round
+    m, e = torch.frexp(w.abs().amax(dim=1) / FP8_MAX)
+    e = torch.where(m == 0.5, e - 1, e)
+    scale = torch.where(m == 0, torch.ones_like(m),
+                        torch.ldexp(torch.ones_like(m), e))
+    return (w / scale[:, None]).to(FP8), scale
+
+
+def dequantize_weight(q: torch.Tensor, scale: torch.Tensor,
+                      dtype=torch.bfloat16) -> torch.Tensor:
+    """``q * scale`` per row in ``dtype`` (exact in bf16 and wider)."""
+    return (q.float() * scale[:, None]).to(dtype)
+
+
 def kernel_serves(weight, ln_weight=None) -> bool:
-    """Whether the kernel takes this ``weight`` [N, K] (and LayerNorm
-    parameter) for up to ``MAX_ROWS`` bf16 rows; the gate is apart."""
-    return (weight.is_cuda and weight.dtype == torch.bfloat16
+    """Whether the kernel takes this ``weight`` [N, K], bf16 or fp8, (and
+    LayerNorm parameter) for up to ``MAX_ROWS`` bf16 rows; the gate is
+    apart."""
+    return (weight.is_cuda and weight.dtype in (torch.bfloat16, FP8)
             and weight.dim() == 2 and weight.shape[1] % 32 == 0
             and weight.shape[1] >= 32
             and (ln_weight is None or ln_weight.dtype == torch.float32)
@@ -103,7 +157,17 @@ def _twin(x, weight, bias, residual, ln_weight, ln_bias, eps, gelu):
     return y.to(dt), x_new
 
 
-def _check(x, weight, bias, residual, ln_weight, ln_bias):
+def _check(x, weight, bias, residual, ln_weight, ln_bias,
+           weight_scale=None):
+    if (weight.dtype == FP8) != (weight_scale is not None):
+        raise ValueError(
+            "a float8_e4m3fn weight and weight_scale come together or not "
+            "at all")
+    if weight_scale is not None and (
+            tuple(weight_scale.shape) != (weight.shape[0],)
+            or weight_scale.dtype != torch.float32):
+        raise ValueError(
+            f"weight_scale must be fp32 [N] = [{weight.shape[0]}]")
     if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
         raise ValueError(
             f"x must be [M, K] and weight [N, K], got {list(x.shape)} and "
@@ -134,16 +198,20 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
                   residual: Optional[torch.Tensor] = None,
                   ln_weight: Optional[torch.Tensor] = None,
                   ln_bias: Optional[torch.Tensor] = None,
-                  eps: float = 1e-5, gelu: bool = False):
-    """``act(LN(x + residual) @ weight.T + bias)`` (module docstring).
+                  eps: float = 1e-5, gelu: bool = False,
+                  weight_scale: Optional[torch.Tensor] = None):
+    """``act(LN(x + residual) @ weight.T + bias)`` (module docstring);
+    ``weight`` is float8_e4m3fn when ``weight_scale`` [N] is given.
     Returns ``y`` [M, N], or ``(y, x_new)`` when ``residual`` is given."""
-    _check(x, weight, bias, residual, ln_weight, ln_bias)
+    _check(x, weight, bias, residual, ln_weight, ln_bias, weight_scale)
     if _kernel_shape(x, weight, ln_weight) and kernel_enabled():
         # the one checked host path: every other operand check is there
         y, x_new = _ext_with("skinny_linear_fwd").skinny_linear_fwd(
             x, weight, bias, residual, ln_weight, ln_bias, float(eps),
-            bool(gelu))
+            bool(gelu), weight_scale)
     else:
+        if weight_scale is not None:
+            weight = dequantize_weight(weight, weight_scale, x.dtype)
         y, x_new = _twin(x, weight, bias, residual, ln_weight, ln_bias, eps,
                          gelu)
     return y if residual is None else (y, x_new)
@@ -166,6 +234,16 @@ def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
     hs = k_cache.shape[-1]
     if ln1.eps != ln2.eps:
         raise ValueError("ln1 and ln2 differ in eps")
+    linears = (c_attn, attn_proj, c_fc, mlp_proj)
+    # (weight, scale) per linear: the fp8 pair where all four carry one
+    # and RLA_SKINNY_FP8 allows it, else the bf16 weight, which holds the
+    # same values
+    if fp8_enabled() and all(
+            getattr(m, "weight_fp8", None) is not None for m in linears):
+        ws = [(m.weight_fp8, m.weight_scale) for m in linears]
+    else:
+        ws = [(m.weight, None) for m in linears]
+    (aw, as_), (pw, ps), (fw, fs), (mw, ms) = ws
     # the one call reaches decode attention's kernel from C++, so that
     # kernel's own gate (RLA_DECODE_ATTN) has to be on as well
     if (_kernel_shape(x, c_attn.weight, ln1.weight) and kernel_enabled()
@@ -173,23 +251,28 @@ def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
             and hs == 64 and k_cache.dtype == torch.bfloat16
             and c_fc.weight.shape[0] % 32 == 0
             and ln2.weight.dtype == torch.float32
-            and all(m.bias is not None
-                    for m in (c_attn, attn_proj, c_fc, mlp_proj))):
+            and all(m.bias is not None for m in linears)):
+        if as_ is not None:
+            return _ext_with("decode_layer_fp8_fwd").decode_layer_fp8_fwd(
+                x, residual, ln1.weight, ln1.bias, aw, as_, c_attn.bias,
+                k_cache, v_cache, pos, int(max_pos), 1.0 / math.sqrt(hs),
+                pw, ps, attn_proj.bias, ln2.weight, ln2.bias, fw, fs,
+                c_fc.bias, mw, ms, mlp_proj.bias, float(ln1.eps))
         return _ext_with("decode_layer_fwd").decode_layer_fwd(
             x, residual, ln1.weight, ln1.bias, c_attn.weight, c_attn.bias,
             k_cache, v_cache, pos, int(max_pos), 1.0 / math.sqrt(hs),
             attn_proj.weight, attn_proj.bias, ln2.weight, ln2.bias,
             c_fc.weight, c_fc.bias, mlp_proj.weight, mlp_proj.bias,
             float(ln1.eps))
-    ln = dict(ln_weight=ln1.weight, ln_bias=ln1.bias, eps=ln1.eps)
+    ln = dict(ln_weight=ln1.weight, ln_bias=ln1.bias, eps=ln1.eps,
+              weight_scale=as_)
     if residual is None:
-        qkv, x1 = skinny_linear(x, c_attn.weight, c_attn.bias, **ln), x
+        qkv, x1 = skinny_linear(x, aw, c_attn.bias, **ln), x
     else:
-        qkv, x1 = skinny_linear(x, c_attn.weight, c_attn.bias,
-                                residual=residual, **ln)
+        qkv, x1 = skinny_linear(x, aw, c_attn.bias, residual=residual, **ln)
     att = decode_attention(qkv, k_cache, v_cache, pos, max_pos)
-    att = skinny_linear(att, attn_proj.weight, attn_proj.bias)
-    hid, x_mid = skinny_linear(att, c_fc.weight, c_fc.bias, residual=x1,
+    att = skinny_linear(att, pw, attn_proj.bias, weight_scale=ps)
+    hid, x_mid = skinny_linear(att, fw, c_fc.bias, residual=x1,
                                ln_weight=ln2.weight, ln_bias=ln2.bias,
-                               eps=ln2.eps, gelu=True)
-    return x_mid, skinny_linear(hid, mlp_proj.weight, mlp_proj.bias)
+                               eps=ln2.eps, gelu=True, weight_scale=fs)
+    return x_mid, skinny_linear(hid, mw, mlp_proj.bias, weight_scale=ms)

@@ -14,6 +14,13 @@ one GPU. Fails without a GPU and the built extension.
                            waves and 16 or 32 weight rows per workgroup
       composed             fused add + LayerNorm kernel, F.linear
                            (hipBLASLt), F.gelu: the model's path
+      f8{n,w}r{1,2}u{8,16}
+                           skinny_linear_fp8_fwd_at on the quantized ring
+                           (not the LM head, which stays bf16): narrow
+                           (8-byte) or wide (16-byte) weight loads, 16 or
+                           32 weight rows per workgroup, 8 or 16
+                           k-steps in flight; its share of 6.29 TB/s is
+                           on the fp8 weight bytes
 
     A decode step visits every layer's weights once, so the timed loop
     walks a ring of 48 weight matrices (8 for the LM head, 1.3 GB) and
@@ -30,6 +37,11 @@ one GPU. Fails without a GPU and the built extension.
     Rule, fixed before the run: _SKINNY_DEFAULT = True iff the decode
     step is faster with the gate on at both B by more than the larger of
     the two contestants' min-max spreads.
+
+(c) The same end to end on a model after quantize_weights_fp8(), with
+    RLA_SKINNY_LINEAR=1: RLA_SKINNY_FP8=1 against =0 (the bf16 kernels on
+    the dequantized weights, the same function). The same rule decides
+    _FP8_DEFAULT.
 """
 import argparse
 import json
@@ -55,6 +67,9 @@ SHAPES = [  # name, N, K, add + LN, GELU, bias, ring
     ("lm_head", 50257, 1600, True, False, False, 8),
 ]
 CONFIGS = {"w4r1": (4, 1), "w8r1": (8, 1), "w8r2": (8, 2)}
+FP8_CONFIGS = {  # row_tiles, wide, uk
+    f"f8{'w' if wide else 'n'}r{rt}u{uk}": (rt, wide, uk)
+    for uk in (16, 8) for wide in (False, True) for rt in (1, 2)}
 
 
 def timed(fn, iters):
@@ -97,6 +112,22 @@ def kernel_point(ext, name, N, K, ln, gelu, bias, ring_n, M, window, rounds):
 
     fns = {k: at(*v) for k, v in CONFIGS.items()}
     fns["composed"] = composed
+    fp8_bytes = {}
+    if name != "lm_head":
+        from ray_lightning_amd.ops.skinny_linear import quantize_weight
+        ring8 = [quantize_weight(w) for w in ring]
+
+        def at8(rows, wide, uk):
+            def run(i):
+                q, s = ring8[i % ring_n]
+                return ext.skinny_linear_fp8_fwd_at(
+                    x, q, s, b, res, gamma, beta, EPS, gelu, rows, wide,
+                    uk)[0]
+            return run
+
+        for k, v in FP8_CONFIGS.items():
+            fns[k] = at8(*v)
+            fp8_bytes[k] = N * K
     diff = (fns["w8r1"](0).float() - composed(0).float()).abs().max().item()
     iters = {}
     for k, fn in fns.items():
@@ -115,12 +146,14 @@ def kernel_point(ext, name, N, K, ln, gelu, bias, ring_n, M, window, rounds):
         med = statistics.median(t)
         out[k] = {"median_us": 1e3 * med, "min_us": 1e3 * min(t),
                   "max_us": 1e3 * max(t),
-                  "share_of_measured_hbm":
-                      2 * N * K / (med * 1e-3) / HBM_MEASURED}
+                  "share_of_measured_hbm": fp8_bytes.get(k, 2 * N * K) /
+                  (med * 1e-3) / HBM_MEASURED}
     return out
 
 
-def end_to_end(rounds):
+def end_to_end(rounds, var="RLA_SKINNY_LINEAR", fp8=False):
+    """The gate `var` on against off; `fp8`: on a quantized model with
+    the skinny kernels on."""
     from ray_lightning_amd.models.gpt2 import (GPT2, GPT2Config,
                                                to_bf16_training)
     P, NEW = 128, 128
@@ -128,12 +161,15 @@ def end_to_end(rounds):
     with torch.device("cuda"):
         model = GPT2(GPT2Config.gpt2_xl())
     model = to_bf16_training(model).eval()
+    if fp8:
+        model.quantize_weights_fp8()
+        os.environ["RLA_SKINNY_LINEAR"] = "1"
     results = []
     for B in (8, 1):
         idx = torch.randint(0, model.cfg.vocab_size, (B, P), device="cuda")
 
         def run(new, gate):
-            os.environ["RLA_SKINNY_LINEAR"] = gate
+            os.environ[var] = gate
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             out = model.generate(idx, new, temperature=0.0)
@@ -167,7 +203,7 @@ def end_to_end(rounds):
         r["gate_on_wins"] = (off["decode_ms_per_step"] -
                              on["decode_ms_per_step"]) > spread
         results.append(r)
-        print(f"# B={B}: on {on['decode_ms_per_step']:.3f} ms/step, off "
+        print(f"# {var} B={B}: on {on['decode_ms_per_step']:.3f} ms/step, off "
               f"{off['decode_ms_per_step']:.3f} ms/step, spread "
               f"{spread:.3f}", flush=True)
     return results
@@ -180,6 +216,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--skip-end-to-end", action="store_true")
+    ap.add_argument("--skip-fp8-end-to-end", action="store_true")
     args = ap.parse_args()
     ext = ops._load_ext() if torch.cuda.is_available() else None
     if ext is None or not hasattr(ext, "skinny_linear_fwd"):
@@ -196,13 +233,18 @@ def main():
             out["kernel"].append(r)
             print(f"# {name} M={M}: " + "  ".join(
                 f"{k} {r[k]['median_us']:.1f}us" for k in
-                (*CONFIGS, "composed")) +
+                (*CONFIGS, "composed", *FP8_CONFIGS) if k in r) +
                 f"  w8r1 {100 * r['w8r1']['share_of_measured_hbm']:.1f}% of "
                 "6.29 TB/s", flush=True)
     if not args.skip_end_to_end:
         out["end_to_end"] = end_to_end(args.rounds)
         out["default_on"] = all(r["gate_on_wins"]
                                 for r in out["end_to_end"])
+    if not args.skip_fp8_end_to_end:
+        out["end_to_end_fp8"] = end_to_end(args.rounds, "RLA_SKINNY_FP8",
+                                           fp8=True)
+        out["fp8_default_on"] = all(r["gate_on_wins"]
+                                    for r in out["end_to_end_fp8"])
     print(json.dumps(out))
 
 
