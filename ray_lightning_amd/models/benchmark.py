@@ -120,7 +120,8 @@ class GPT2LM(LightningModule):
                  gen_eos_id: Optional[int] = None,
                  gen_top_p: Optional[float] = None,
                  gen_seed=None, *, gen_draft_tokens: int = 0,
-                 gen_draft_ngram: int = 3, gen_fp8_weights: bool = False):
+                 gen_draft_ngram: int = 3, gen_fp8_weights: bool = False,
+                 gen_fp8_kv: bool = False):
         super().__init__()
         self.save_hyperparameters()
         # predict_step: how GPT2.generate continues a batch of prompts
@@ -136,6 +137,10 @@ class GPT2LM(LightningModule):
         # applied once, before the first predict_step
         self.gen_fp8_weights = gen_fp8_weights
         self._fp8_quantized = False
+        # fp8 KV cache for predict_step (GPT2.generate(kv_fp8=True))
+        if gen_fp8_kv and not bf16_weights:
+            raise ValueError("gen_fp8_kv needs bf16_weights=True")
+        self.gen_fp8_kv = gen_fp8_kv
         # packed rows: when set, training_step derives document ids from
         # this EOS token and attention / positions stay within documents
         self.doc_eos_id = doc_eos_id
@@ -194,7 +199,7 @@ class GPT2LM(LightningModule):
             temperature=self.gen_temperature, top_k=self.gen_top_k,
             eos_token_id=self.gen_eos_id, top_p=self.gen_top_p,
             seed=self.gen_seed, draft_tokens=self.gen_draft_tokens,
-            draft_ngram=self.gen_draft_ngram)
+            draft_ngram=self.gen_draft_ngram, kv_fp8=self.gen_fp8_kv)
 
     def configure_optimizers(self):
         decay, no_decay = [], []

@@ -33,6 +33,8 @@ with at most 64 rows runs every block as one ``decode_layer`` call and
 the final LayerNorm with the LM head as one ``skinny_linear`` call
 (ops/skinny_linear.py). After ``GPT2.quantize_weights_fp8()`` those decode
 steps stream the blocks' linear weights as fp8 (``RLA_SKINNY_FP8``).
+``generate(kv_fp8=True)`` keeps the KV cache in fp8 (ops/decode_attn.py,
+docs/DESIGN.md §20).
 """
 from __future__ import annotations
 
@@ -99,22 +101,31 @@ class CausalSelfAttention(nn.Module):
         does without a cache and copies its k and v into the caches at
         ``[:, :, :T]``; after it, ``x`` is one new token per row and
         attention is ``decode_attention`` over the cache, or, with
-        ``extend``, ``T`` new tokens per row and ``append_attention``."""
+        ``extend``, ``T`` new tokens per row and ``append_attention``. An
+        fp8 cache's layer is ``(k_cache, v_cache, kv, k_scale, v_scale)``
+        and is filled by ``kv_cache_fill``."""
         B, T, C = x.shape
         qkv = self.c_attn(x)
+        scales = {}
+        if cache is not None and len(cache) == 5:
+            scales = dict(k_scale=cache[3], v_scale=cache[4])
+            cache = cache[:3]
         if extend:
             from ..ops.append_attn import append_attention
             k_cache, v_cache, kv = cache
             y = append_attention(qkv, k_cache, v_cache, kv.pos, kv.max_pos,
-                                 self.n_head)
+                                 self.n_head, **scales)
             return self.c_proj(y)
         if cache is not None and cache[2].prefilled:
             from ..ops.decode_attn import decode_attention
             k_cache, v_cache, kv = cache
             y = decode_attention(qkv.view(B, 3 * C), k_cache, v_cache,
-                                 kv.pos, kv.max_pos, self.n_head)
+                                 kv.pos, kv.max_pos, self.n_head, **scales)
             return self.c_proj(y.view(B, 1, C))
-        if cache is not None:
+        if scales:
+            from ..ops.decode_attn import kv_cache_fill
+            kv_cache_fill(qkv, cache[0], cache[1], **scales)
+        elif cache is not None:
             # the prefill's cache fill, from the strided k and v views
             hs = C // self.n_head
             _, k, v = qkv.split(C, dim=2)
@@ -316,7 +327,7 @@ class GPT2(nn.Module):
                 attn_out = block.attn(h, bounds)
             else:
                 attn_out = block.attn(
-                    h, None, (cache.k[i], cache.v[i], cache), extend)
+                    h, None, self._layer_cache(cache, i), extend)
             x, h = block.ln_2(attn_out, residual=x, dropout_p=pr)
             mlp_out = block.mlp(h)
             next_ln = (self.h[i + 1].ln_1 if i + 1 < len(self.h)
@@ -331,6 +342,15 @@ class GPT2(nn.Module):
                 torch.full((B,), T, dtype=torch.int32, device=idx.device),
                 T)
         return h  # = ln_f(x)
+
+    @staticmethod
+    def _layer_cache(cache, i):
+        """Layer ``i`` of ``cache`` as ``CausalSelfAttention.forward``
+        takes it: with the scales when the cache is fp8."""
+        if cache.k_scale is None:
+            return (cache.k[i], cache.v[i], cache)
+        return (cache.k[i], cache.v[i], cache, cache.k_scale[i],
+                cache.v_scale[i])
 
     @torch.no_grad()
     def quantize_weights_fp8(self) -> "GPT2":
@@ -394,11 +414,13 @@ class GPT2(nn.Module):
                 f"the cache holds {cache.Tmax} positions per row")
         x = self.wte(idx[:, 0]) + self.wpe(cache.pos.to(torch.int64))
         res = None
+        ks, vs = cache.k_scale, cache.v_scale
         for i, block in enumerate(self.h):
             res, x = decode_layer(
                 x, res, block.ln_1, block.attn.c_attn, cache.k[i],
                 cache.v[i], cache.pos, cache.max_pos, block.attn.c_proj,
-                block.ln_2, block.mlp.c_fc, block.mlp.c_proj)
+                block.ln_2, block.mlp.c_fc, block.mlp.c_proj,
+                *(() if ks is None else (ks[i], vs[i])))
         logits, _ = skinny_linear(
             x, self.lm_head.weight, None, residual=res,
             ln_weight=self.ln_f.weight, ln_bias=self.ln_f.bias,
@@ -462,7 +484,7 @@ class GPT2(nn.Module):
                  prefill_chunk: Optional[int] = None,
                  top_p: Optional[float] = None, seed=None,
                  draft_tokens: int = 0, draft_ngram: int = 3,
-                 return_stats: bool = False):
+                 return_stats: bool = False, kv_fp8: bool = False):
         """Sample ``max_new_tokens`` tokens per row after the prompts.
 
         ``idx`` [B, P] holds the prompts, right-padded; ``prompt_lens``
@@ -525,10 +547,22 @@ class GPT2(nn.Module):
         extend forwards run, "committed": tokens they committed over all
         rows}`` (both 0 without drafts).
 
+        ``kv_fp8=True`` keeps the KV cache as float8_e4m3fn codes with one
+        power-of-two scale per head and position (ops/decode_attn.py): 136
+        bytes where bf16 takes 256, read by the fp8 decode-attention kernel
+        and filled by ``kv_cache_fill`` after the prefill. Every token
+        attends the dequantized values, its own included. It needs a bf16
+        model with head size 64 (``ValueError`` otherwise); ``prefill_chunk``
+        and ``draft_tokens`` work with it through a torch composition.
+
         Runs without gradients, in eval mode; the module's mode is put
         back afterwards."""
         from ..ops.decode_attn import KVCache, decode_attn_chunk
         cfg = self.cfg
+        if kv_fp8 and (self.wte.weight.dtype != torch.bfloat16
+                       or cfg.n_embd // cfg.n_head != 64):
+            raise ValueError(
+                "kv_fp8 needs a bf16 model with head size 64")
         if idx.dim() != 2:
             raise ValueError("idx must be [B, P]")
         B, P = idx.shape
@@ -607,7 +641,9 @@ class GPT2(nn.Module):
                 Tmax = max(min(Tmax, cfg.n_positions), P_pad)
                 p0 = self.wte.weight
                 cache = KVCache(cfg.n_layer, B, cfg.n_head, Tmax,
-                                cfg.n_embd // cfg.n_head, p0.dtype, dev)
+                                cfg.n_embd // cfg.n_head,
+                                torch.float8_e4m3fn if kv_fp8 else p0.dtype,
+                                dev)
             rows = torch.arange(B, device=dev)
             if prefill_chunk is None:
                 h = self._hidden(prompt, None, cache)

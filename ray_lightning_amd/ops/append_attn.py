@@ -29,6 +29,13 @@ is ``_APPEND_DEFAULT`` below; ``RLA_APPEND_ATTN=1`` / ``=0`` forces it on
 runs the torch twin with the same semantics: ``scatter_`` into the
 caches, then a masked softmax in fp32 (on the GPU: SDPA with the same
 mask).
+
+Over an fp8 cache (``k_scale`` / ``v_scale`` given, ops/decode_attn.py) the
+call is a torch composition on the same contract as ``decode_attention``:
+the ``T`` new rows are quantized and stored as codes and scales, the caches
+are dequantized into bf16 temporaries, and the bf16 path above (kernel or
+twin) attends those with the new rows' dequantized values. Correct, not
+fast: the MFMA kernel has no fp8 variant yet.
 """
 from __future__ import annotations
 
@@ -108,12 +115,48 @@ def _twin(qkv, k_cache, v_cache, pos, max_pos):
     return o.transpose(1, 2).reshape(B, T, H * hs)
 
 
+def _fp8(qkv, k_cache, v_cache, k_scale, v_scale, pos, max_pos):
+    """Quantize and store the new rows, then the bf16 op on dequantized
+    temporaries (module docstring)."""
+    from .decode_attn import dequantize_kv, quantize_kv
+    B, H, Tmax, hs = k_cache.shape
+    T = qkv.shape[1]
+    parts = qkv.view(B, T, 3, H, hs).unbind(2)
+    active = (pos >= 0) & (pos <= max_pos)
+    slot = pos.clamp(0, Tmax - T).to(torch.int64)[:, None] + \
+        torch.arange(T, device=qkv.device)                      # [B, T]
+    index = slot.view(B, 1, T).expand(B, H, T)
+    idx4 = index.unsqueeze(3).expand(B, H, T, hs)
+    keep = active.view(B, 1, 1)
+    new = [parts[0]]
+    for cache, scale, x in ((k_cache, k_scale, parts[1]),
+                            (v_cache, v_scale, parts[2])):
+        codes, s = quantize_kv(x.transpose(1, 2))               # [B, H, T, .]
+        # inactive rows write back what they read; fp8 moves as bytes
+        bytes_ = cache.view(torch.uint8)
+        bytes_.scatter_(2, idx4, torch.where(
+            keep.unsqueeze(3), codes.view(torch.uint8),
+            bytes_.gather(2, idx4)))
+        scale.scatter_(2, index, torch.where(keep, s,
+                                             scale.gather(2, index)))
+        new.append(dequantize_kv(codes, s, qkv.dtype).transpose(1, 2))
+    # slots not held yet may carry the NaN code or a NaN scale; the bf16
+    # op never attends them, as it never attends NaN in a bf16 cache
+    return append_attention(
+        torch.stack(new, dim=2).reshape(B, T, 3 * H * hs),
+        dequantize_kv(k_cache, k_scale, qkv.dtype),
+        dequantize_kv(v_cache, v_scale, qkv.dtype), pos, max_pos)
+
+
 def append_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, pos: torch.Tensor,
                      max_pos: Optional[int] = None,
-                     n_head: Optional[int] = None) -> torch.Tensor:
+                     n_head: Optional[int] = None,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``T`` new tokens per row against the KV cache, with the append
-    (module docstring). ``n_head``, when given, must be the caches' H."""
+    (module docstring). ``n_head``, when given, must be the caches' H.
+    ``k_scale`` / ``v_scale`` come with float8_e4m3fn caches."""
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
         raise ValueError("k_cache and v_cache must share one "
                          "[B, H, Tmax, hs] shape")
@@ -122,6 +165,24 @@ def append_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
         raise ValueError(f"n_head = {n_head}, the caches hold {H} heads")
     if max_pos is None:
         max_pos = Tmax - (qkv.shape[1] if qkv.dim() == 3 else 1)
+    from .decode_attn import _check_scales
+    _check_scales(k_cache, v_cache, k_scale, v_scale)
+    if k_scale is not None:
+        if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] < 1 \
+                or qkv.shape[2] != 3 * H * hs:
+            raise ValueError(
+                f"qkv must be [B, T, 3*H*hs] = [{B}, T >= 1, {3 * H * hs}], "
+                f"got {list(qkv.shape)}")
+        if pos.dtype != torch.int32 or tuple(pos.shape) != (B,) \
+                or pos.device != qkv.device or k_cache.device != qkv.device:
+            raise ValueError("pos must be int32 [B] and the caches on "
+                             "qkv's device")
+        if not (0 <= max_pos and max_pos + qkv.shape[1] <= Tmax):
+            raise ValueError(
+                f"max_pos = {max_pos} with T = {qkv.shape[1]} new tokens "
+                f"does not fit Tmax = {Tmax}")
+        return _fp8(qkv.contiguous(), k_cache, v_cache, k_scale, v_scale,
+                    pos, int(max_pos))
     if _kernel_shape(qkv, k_cache) and _kernel_enabled():
         ext = _load_ext()
         if not hasattr(ext, "append_attn_fwd"):

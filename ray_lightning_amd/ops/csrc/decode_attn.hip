@@ -29,6 +29,24 @@
 //    qkv and stores the same 16-byte vectors to the caches at slot pos[b].
 //    It is the only reader and the only writer of that slot in the launch.
 //
+// fp8 cache (decode_attn_fp8_partial_kernel, docs/DESIGN.md §20): K and V
+// are OCP float8_e4m3fn codes with one fp32 power-of-two scale per (b, h,
+// position), [B, H, Tmax]. The same grid, chunks, partials and combine,
+// with a data path of its own:
+//  - a 64-byte row is 4 lanes x 16 bytes: one wave load covers 16
+//    positions (1 KiB contiguous) and one of the workgroup (2 waves) 32, q
+//    is 16 fp32 per lane, a dot product folds over 4 lanes;
+//  - a chunk's 128 K scales and 128 V scales are loaded once per workgroup
+//    into LDS; codes become fp32 in registers (v_cvt_scalef32_pk_f32_fp8,
+//    scale operand 1.0); the scales multiply the score and the probability,
+//    once per position: s = (q . kq) * ks[t], acc += (p * vs[t]) * vq;
+//  - the group that owns slot pos[b] quantizes the new k / v row (absmax
+//    over its 4 lanes, kv_fp8_core.h), stores codes and scales, and attends
+//    the codes it stored, so the output is attention over the updated cache;
+//  - the 16 groups of a wave are folded by a halving exchange, 15 shuffles
+//    for the 16 accumulators of a lane.
+// kv_cache_fill_kernel quantizes the prefill's k and v into the caches.
+//
 // pos is read on the device only. A row whose pos[b] lies outside
 // [0, max_pos] is inactive: all its positions are invalid, so it forms no
 // address from pos[b], stores nothing and its output is zero.
@@ -38,7 +56,11 @@
 #include <ATen/hip/HIPContext.h>
 #include <cmath>
 
+#include "kv_fp8_core.h"
+
 namespace {
+
+using OptTensor = c10::optional<torch::Tensor>;
 
 constexpr int kDaThreads = 256;
 constexpr int kDaWaves = kDaThreads / 64;
@@ -48,6 +70,10 @@ constexpr int kDaPartial = kDaHs + 2;  // floats: 64 acc, max, sum
 // KV positions per workgroup; profiles/gpt2_generate.md has the
 // alternatives measured
 constexpr int kDaChunk = 128;
+// waves per workgroup of the fp8-cache kernel: 2 (four K and four V loads
+// in flight per thread) beat 4 at five of the six points measured in
+// profiles/kv_fp8.md
+constexpr int kDaFp8Waves = 2;
 
 __device__ __forceinline__ void bf16x8_to_float(const uint4& raw,
                                                 float* f) {
@@ -233,6 +259,371 @@ __global__ __launch_bounds__(kDaHs) void decode_attn_combine_kernel(
   o[(long)bh * kDaHs + t] = *reinterpret_cast<const unsigned short*>(&ob);
 }
 
+// ---- fp8 KV cache (file header, "fp8 cache") ----------------------------
+
+// 4 e4m3 bytes of `w` as fp32, low byte first. The scale operand is 1.0, so
+// the conversion is exact.
+__device__ __forceinline__ void fp8x4_to_float(unsigned w, float* f) {
+  const auto lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, 1.f, false);
+  const auto hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, 1.f, true);
+  f[0] = lo[0];
+  f[1] = lo[1];
+  f[2] = hi[0];
+  f[3] = hi[1];
+}
+
+__device__ __forceinline__ void fp8x16_to_float(const uint4& raw, float* f) {
+  fp8x4_to_float(raw.x, f);
+  fp8x4_to_float(raw.y, f + 4);
+  fp8x4_to_float(raw.z, f + 8);
+  fp8x4_to_float(raw.w, f + 12);
+}
+
+// largest |x| of 16 bf16 values, as fp32 bits (non-finite values sort on
+// top, which is what kv_scale_bits wants)
+__device__ __forceinline__ unsigned kv_amax16(const uint4& a, const uint4& b) {
+  const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  unsigned m = 0;
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    m = max(m, (w[i] << 16) & 0x7fff0000u);
+    m = max(m, w[i] & 0x7fff0000u);
+  }
+  return m;
+}
+
+// 16 bf16 values as 16 e4m3 codes under scale 2^(se - 127), low byte first
+__device__ __forceinline__ uint4 kv_quant16(const uint4& a, const uint4& b,
+                                            int se) {
+  const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  unsigned o[4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i)
+    o[i] = kv_quant(w[2 * i] & 0xffffu, se) |
+           kv_quant(w[2 * i] >> 16, se) << 8 |
+           kv_quant(w[2 * i + 1] & 0xffffu, se) << 16 |
+           kv_quant(w[2 * i + 1] >> 16, se) << 24;
+  return uint4{o[0], o[1], o[2], o[3]};
+}
+
+// A row of 64 bf16 is held by 4 adjacent lanes, 16 values each (a, b).
+// Its absmax as fp32 bits; every lane of the wave runs the shuffles.
+__device__ __forceinline__ unsigned kv_row_amax(const uint4& a,
+                                                const uint4& b) {
+  unsigned amax = kv_amax16(a, b);
+  amax = max(amax, (unsigned)__shfl_xor((int)amax, 1, 64));
+  amax = max(amax, (unsigned)__shfl_xor((int)amax, 2, 64));
+  return amax;
+}
+
+// This lane's 16 codes of the row with that absmax. A zero row has scale 1
+// (its codes are signed zeros); a non-finite one gets the NaN code next to
+// its NaN scale.
+__device__ __forceinline__ uint4 kv_quant_row(const uint4& a, const uint4& b,
+                                              unsigned amax) {
+  if (amax >= 0x7f800000u)
+    return uint4{0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu};
+  return kv_quant16(a, b, amax == 0 ? 127 : kv_scale_exp(amax));
+}
+
+// The partial kernel over an fp8 cache: the grid, the chunk partition, the
+// partial's layout and the folds are decode_attn_partial_kernel's, so the
+// combine kernel serves both. Its own: a 64-byte row is 4 lanes x 16
+// bytes, one wave load covers 16 positions; the chunk's scales go through
+// LDS once; the 16 groups of a wave are folded by a halving exchange that
+// leaves every lane one accumulator.
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void decode_attn_fp8_partial_kernel(
+    const unsigned short* __restrict__ qkv,  // [B, 3*H*64] bf16
+    unsigned char* __restrict__ k_cache,     // [B, H, Tmax, 64] e4m3
+    unsigned char* __restrict__ v_cache,     // [B, H, Tmax, 64] e4m3
+    float* __restrict__ k_scale,             // [B, H, Tmax]
+    float* __restrict__ v_scale,             // [B, H, Tmax]
+    const int* __restrict__ pos,             // [B]
+    float* __restrict__ ws,                  // [B*H, gridDim.x, 66]
+    int H, int Tmax, int max_pos, float scale_log2e) {
+  constexpr int THREADS = WAVES * 64;
+  constexpr int STEP = WAVES * 16;     // positions per workgroup load
+  constexpr int U = kDaChunk / STEP;   // positions per thread group
+  static_assert(kDaChunk % STEP == 0, "the chunk must be whole loads");
+  __shared__ float lds_scale[2][kDaChunk];  // K, then V
+  __shared__ float lds_acc[WAVES][kDaHs];
+  __shared__ float lds_ml[WAVES][2];
+
+  const int chunk = blockIdx.x;
+  const int bh = blockIdx.y;
+  const int b = bh / H;
+  const int h = bh - b * H;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int sub = lane & 3;   // which 16 bytes of the 64-byte row
+  const int grp = lane >> 2;  // which of the wave's 16 positions
+
+  const int pb = pos[b];
+  const int last = (pb >= 0 && pb <= max_pos) ? pb : -1;
+  float* __restrict__ part =
+      ws + ((long)bh * gridDim.x + chunk) * kDaPartial;
+  const int c0 = chunk * kDaChunk;
+
+  if (c0 > last) {  // uniform: nothing of this row in here
+    if (threadIdx.x < kDaHs) part[threadIdx.x] = 0.f;
+    if (threadIdx.x == 0) {
+      part[kDaHs] = -INFINITY;
+      part[kDaHs + 1] = 0.f;
+    }
+    return;
+  }
+
+  // the scales of the chunk's cached positions, one load per workgroup;
+  // slot `last` and above are not read (0 <= p < last <= max_pos < Tmax)
+  const long scale_row = (long)bh * Tmax;
+  for (int i = threadIdx.x; i < 2 * kDaChunk; i += THREADS) {
+    const int which = i / kDaChunk, p = c0 + (i & (kDaChunk - 1));
+    float s = 0.f;
+    if (p < last) s = (which ? v_scale : k_scale)[scale_row + p];
+    lds_scale[which][i & (kDaChunk - 1)] = s;
+  }
+
+  const long C = (long)H * kDaHs;
+  const unsigned short* __restrict__ qrow =
+      qkv + (long)b * 3 * C + h * kDaHs + sub * 16;
+  const long cache_row = (long)bh * Tmax * kDaHs + sub * 16;  // bytes
+
+  // all loads first: q, this thread's U rows of K and of V, and the new
+  // row's k and v (bf16, from qkv) in the group that meets slot `last`
+  const uint4 q0 = *reinterpret_cast<const uint4*>(qrow);
+  const uint4 q1 = *reinterpret_cast<const uint4*>(qrow + 8);
+  uint4 kraw[U], vraw[U];
+  const int p0 = c0 + wave * 16 + grp;
+  bool own = false;
+  #pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int p = p0 + u * STEP;
+    kraw[u] = uint4{0, 0, 0, 0};
+    vraw[u] = uint4{0, 0, 0, 0};
+    own = own || p == last;
+    if (p < last) {
+      const long off = cache_row + (long)p * kDaHs;
+      kraw[u] = *reinterpret_cast<const uint4*>(k_cache + off);
+      vraw[u] = *reinterpret_cast<const uint4*>(v_cache + off);
+    }
+  }
+  uint4 nk0 = uint4{0, 0, 0, 0}, nk1 = nk0, nv0 = nk0, nv1 = nk0;
+  if (own) {
+    nk0 = *reinterpret_cast<const uint4*>(qrow + C);
+    nk1 = *reinterpret_cast<const uint4*>(qrow + C + 8);
+    nv0 = *reinterpret_cast<const uint4*>(qrow + 2 * C);
+    nv1 = *reinterpret_cast<const uint4*>(qrow + 2 * C + 8);
+  }
+
+  // quantize the new row (every lane runs the absmax shuffles, the owning
+  // group alone the conversion) and store it: one writer, and no reader,
+  // of slot `last`
+  const unsigned nk_amax = kv_row_amax(nk0, nk1);
+  const unsigned nv_amax = kv_row_amax(nv0, nv1);
+  const unsigned nks_bits = kv_scale_bits(nk_amax);
+  const unsigned nvs_bits = kv_scale_bits(nv_amax);
+  uint4 nkq = uint4{0, 0, 0, 0}, nvq = nkq;
+  if (own) {
+    nkq = kv_quant_row(nk0, nk1, nk_amax);
+    nvq = kv_quant_row(nv0, nv1, nv_amax);
+    const long off = cache_row + (long)last * kDaHs;
+    *reinterpret_cast<uint4*>(k_cache + off) = nkq;
+    *reinterpret_cast<uint4*>(v_cache + off) = nvq;
+    if (sub == 0) {
+      k_scale[scale_row + last] = __uint_as_float(nks_bits);
+      v_scale[scale_row + last] = __uint_as_float(nvs_bits);
+    }
+  }
+  __syncthreads();  // lds_scale
+
+  float q[16];
+  bf16x8_to_float(q0, q);
+  bf16x8_to_float(q1, q + 8);
+  #pragma unroll
+  for (int j = 0; j < 16; ++j) q[j] *= scale_log2e;
+
+  // scores (in units of log 2): (q . codes) * scale[p], exact in the scale
+  float s[U], vs[U];
+  float m = -INFINITY;
+  #pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int p = p0 + u * STEP;
+    const int i = p - c0;
+    float ks = lds_scale[0][i];
+    vs[u] = lds_scale[1][i];
+    if (p == last) {  // attends what it stored: the dequantized new row
+      kraw[u] = nkq;
+      vraw[u] = nvq;
+      ks = __uint_as_float(nks_bits);
+      vs[u] = __uint_as_float(nvs_bits);
+    }
+    float kf[16];
+    fp8x16_to_float(kraw[u], kf);
+    float d = 0.f;
+    #pragma unroll
+    for (int j = 0; j < 16; ++j) d = fmaf(q[j], kf[j], d);
+    d += __shfl_xor(d, 1, 64);
+    d += __shfl_xor(d, 2, 64);
+    s[u] = p <= last ? d * ks : -INFINITY;
+    m = fmaxf(m, s[u]);
+  }
+
+  float l = 0.f;
+  float acc[16];
+  #pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+  #pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float pr = s[u] == -INFINITY ? 0.f : exp2f(s[u] - m);
+    float vf[16];
+    fp8x16_to_float(vraw[u], vf);
+    l += pr;
+    const float pv = pr * vs[u];
+    #pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = fmaf(pv, vf[j], acc[j]);
+  }
+
+  // fold the wave's 16 thread groups: common max, rescale, then a halving
+  // exchange over lane bits 2 .. 5. At each step a lane keeps one half of
+  // its accumulators and adds the partner's copy of that half, so after 4
+  // steps (8 + 4 + 2 + 1 shuffles) lane (grp, sub) holds the wave's sum of
+  // accumulator sub*16 + bitrev4(grp). The tree is fixed: same bits always.
+  float mw = m;
+  #pragma unroll
+  for (int off = 4; off < 64; off <<= 1)
+    mw = fmaxf(mw, __shfl_xor(mw, off, 64));
+  const float f = m == -INFINITY ? 0.f : exp2f(m - mw);
+  l *= f;
+  #pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] *= f;
+  #pragma unroll
+  for (int off = 4; off < 64; off <<= 1) l += __shfl_xor(l, off, 64);
+  int idx = sub * 16;
+  #pragma unroll
+  for (int n = 8, off = 4; n >= 1; n >>= 1, off <<= 1) {
+    const bool up = lane & off;
+    #pragma unroll
+    for (int j = 0; j < n; ++j) {
+      const float keep = up ? acc[j + n] : acc[j];
+      const float send = up ? acc[j] : acc[j + n];
+      acc[j] = keep + __shfl_xor(send, off, 64);
+    }
+    idx += up ? n : 0;
+  }
+  lds_acc[wave][idx] = acc[0];
+  if (lane == 0) {
+    lds_ml[wave][0] = mw;
+    lds_ml[wave][1] = l;
+  }
+  __syncthreads();
+
+  // fold the waves in wave order; thread t owns accumulator t
+  if (threadIdx.x < kDaHs) {
+    float M = lds_ml[0][0];
+    #pragma unroll
+    for (int w = 1; w < WAVES; ++w) M = fmaxf(M, lds_ml[w][0]);
+    float L = 0.f, A = 0.f;
+    #pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const float mwv = lds_ml[w][0];
+      const float fw = mwv == -INFINITY ? 0.f : exp2f(mwv - M);
+      L = fmaf(lds_ml[w][1], fw, L);
+      A = fmaf(lds_acc[w][threadIdx.x], fw, A);
+    }
+    part[threadIdx.x] = A;
+    if (threadIdx.x == 0) {
+      part[kDaHs] = M;
+      part[kDaHs + 1] = L;
+    }
+  }
+}
+
+// The prefill's cache fill: k and v of qkv [B, T, 3*H*64] quantized into
+// slots 0 .. T-1. One 4-lane group per (k | v, b, h, t) row, t fastest: a
+// wave reads 16 full 128-byte lines and writes 1 KiB of codes and 64 bytes
+// of scales, both contiguous. Slots >= T are not touched.
+__global__ __launch_bounds__(256) void kv_cache_fill_kernel(
+    const unsigned short* __restrict__ qkv,
+    unsigned char* __restrict__ k_cache, unsigned char* __restrict__ v_cache,
+    float* __restrict__ k_scale, float* __restrict__ v_scale, int B, int T,
+    int H, int Tmax) {
+  const long rows = (long)B * H * T;  // per cache
+  const long r = ((long)blockIdx.x * 256 + threadIdx.x) >> 2;
+  const int sub = threadIdx.x & 3;
+  const bool live = r < 2 * rows;  // uniform over the 4 lanes of a row
+  const int which = live && r >= rows;
+  const long rr = live ? r - which * rows : 0;
+  const int t = (int)(rr % T);
+  const long bhi = rr / T;  // b * H + h
+  const int b = (int)(bhi / H);
+  const int h = (int)(bhi - (long)b * H);
+  const long C = (long)H * kDaHs;
+  uint4 a = uint4{0, 0, 0, 0}, c = a;
+  if (live) {
+    const unsigned short* src = qkv + ((long)b * T + t) * 3 * C +
+                                (1 + which) * C + h * kDaHs + sub * 16;
+    a = *reinterpret_cast<const uint4*>(src);
+    c = *reinterpret_cast<const uint4*>(src + 8);
+  }
+  const unsigned amax = kv_row_amax(a, c);
+  if (live) {
+    const uint4 codes = kv_quant_row(a, c, amax);
+    const unsigned scale_bits = kv_scale_bits(amax);
+    const long slot = bhi * Tmax + t;
+    *reinterpret_cast<uint4*>((which ? v_cache : k_cache) + slot * kDaHs +
+                              sub * 16) = codes;
+    if (sub == 0)
+      (which ? v_scale : k_scale)[slot] = __uint_as_float(scale_bits);
+  }
+}
+
+template <int WAVES>
+void da_fp8_launch(const torch::Tensor& qkv, torch::Tensor& k_cache,
+                   torch::Tensor& v_cache, torch::Tensor& k_scale,
+                   torch::Tensor& v_scale, const torch::Tensor& pos,
+                   torch::Tensor& ws, torch::Tensor& o, int B, int H,
+                   int Tmax, int max_pos, int n_chunks, float scale_log2e) {
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  hipLaunchKernelGGL(
+      (decode_attn_fp8_partial_kernel<WAVES>), dim3(n_chunks, B * H),
+      dim3(WAVES * 64), 0, stream,
+      reinterpret_cast<const unsigned short*>(qkv.data_ptr()),
+      reinterpret_cast<unsigned char*>(k_cache.data_ptr()),
+      reinterpret_cast<unsigned char*>(v_cache.data_ptr()),
+      k_scale.data_ptr<float>(), v_scale.data_ptr<float>(),
+      pos.data_ptr<int>(), ws.data_ptr<float>(), H, Tmax, max_pos,
+      scale_log2e);
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(B * H), dim3(kDaHs),
+                     0, stream, ws.data_ptr<float>(),
+                     reinterpret_cast<unsigned short*>(o.data_ptr()),
+                     n_chunks);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "decode_attn_fwd: ", hipGetErrorString(e));
+}
+
+// what a pair of fp8 caches and their scales must be, for `who`
+void kv_fp8_check(const char* who, const torch::Tensor& k_cache,
+                  const torch::Tensor& v_cache, const torch::Tensor& k_scale,
+                  const torch::Tensor& v_scale, const at::Device& dev) {
+  for (const torch::Tensor* c : {&k_cache, &v_cache})
+    TORCH_CHECK(c->is_cuda() && c->device() == dev &&
+                c->scalar_type() == at::kFloat8_e4m3fn && c->dim() == 4 &&
+                c->is_contiguous() && c->size(3) == kDaHs,
+                who, ": with scales, k_cache and v_cache must be contiguous "
+                "float8_e4m3fn [B, H, Tmax, 64] on qkv's device");
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), who,
+              ": k_cache and v_cache differ in shape");
+  for (const torch::Tensor* s : {&k_scale, &v_scale})
+    TORCH_CHECK(s->is_cuda() && s->device() == dev &&
+                s->scalar_type() == at::kFloat && s->dim() == 3 &&
+                s->is_contiguous() && s->size(0) == k_cache.size(0) &&
+                s->size(1) == k_cache.size(1) &&
+                s->size(2) == k_cache.size(2),
+                who, ": k_scale and v_scale must be contiguous fp32 "
+                "[B, H, Tmax] on qkv's device");
+}
+
 template <int CHUNK>
 void da_launch(const torch::Tensor& qkv, torch::Tensor& k_cache,
                torch::Tensor& v_cache, const torch::Tensor& pos,
@@ -256,18 +647,34 @@ void da_launch(const torch::Tensor& qkv, torch::Tensor& k_cache,
 }
 
 // every check happens here, before anything is allocated or launched
+// With scales the caches are fp8 and `waves` picks the fp8 kernel's
+// workgroup size.
 torch::Tensor da_checked(torch::Tensor qkv, torch::Tensor k_cache,
                          torch::Tensor v_cache, torch::Tensor pos,
-                         int64_t max_pos, double scale, int64_t chunk) {
+                         int64_t max_pos, double scale, int64_t chunk,
+                         OptTensor k_scale = OptTensor(),
+                         OptTensor v_scale = OptTensor(),
+                         int64_t waves = kDaFp8Waves) {
   constexpr int64_t kLimit = (int64_t)1 << 31;
+  const bool fp8 = k_scale.has_value();
+  TORCH_CHECK(fp8 == v_scale.has_value(),
+              "decode_attn_fwd: k_scale and v_scale come together or not "
+              "at all");
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 &&
               qkv.dim() == 2 && qkv.is_contiguous(),
               "decode_attn_fwd: qkv must be a contiguous bf16 GPU tensor "
               "[B, 3*H*64]");
+  if (fp8) {
+    kv_fp8_check("decode_attn_fwd", k_cache, v_cache, *k_scale, *v_scale,
+                 qkv.device());
+    TORCH_CHECK(chunk == kDaChunk && (waves == 2 || waves == 4),
+                "decode_attn_fwd: the fp8 kernel has chunk = ", kDaChunk,
+                " and 2 or 4 waves");
+  }
   for (const torch::Tensor* c : {&k_cache, &v_cache})
-    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() &&
-                c->scalar_type() == at::kBFloat16 && c->dim() == 4 &&
-                c->is_contiguous() && c->size(3) == kDaHs,
+    TORCH_CHECK(fp8 || (c->is_cuda() && c->device() == qkv.device() &&
+                        c->scalar_type() == at::kBFloat16 && c->dim() == 4 &&
+                        c->is_contiguous() && c->size(3) == kDaHs),
                 "decode_attn_fwd: k_cache and v_cache must be contiguous "
                 "bf16 [B, H, Tmax, 64] on qkv's device");
   TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
@@ -306,6 +713,17 @@ torch::Tensor da_checked(torch::Tensor qkv, torch::Tensor k_cache,
   auto ws = torch::empty({B * H, n_chunks, kDaPartial},
                          qkv.options().dtype(at::kFloat));
   const float scale_log2e = (float)(scale * 1.4426950408889634);
+  if (fp8) {
+    if (waves == 2)
+      da_fp8_launch<2>(qkv, k_cache, v_cache, *k_scale, *v_scale, pos, ws, o,
+                       (int)B, (int)H, (int)Tmax, (int)max_pos,
+                       (int)n_chunks, scale_log2e);
+    else
+      da_fp8_launch<4>(qkv, k_cache, v_cache, *k_scale, *v_scale, pos, ws, o,
+                       (int)B, (int)H, (int)Tmax, (int)max_pos,
+                       (int)n_chunks, scale_log2e);
+    return o;
+  }
 #define DA_CASE(CH)                                                     \
   if (chunk == CH)                                                      \
     da_launch<CH>(qkv, k_cache, v_cache, pos, ws, o, (int)B, (int)H,    \
@@ -323,8 +741,62 @@ long decode_attn_chunk() { return kDaChunk; }
 
 torch::Tensor decode_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
-                              int64_t max_pos, double scale) {
-  return da_checked(qkv, k_cache, v_cache, pos, max_pos, scale, kDaChunk);
+                              int64_t max_pos, double scale,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale) {
+  return da_checked(qkv, k_cache, v_cache, pos, max_pos, scale, kDaChunk,
+                    k_scale, v_scale);
+}
+
+// the fp8-cache op at 2 or 4 waves per workgroup, for the measurement that
+// picks kDaFp8Waves (scripts/bench_kv_fp8.py); nothing else calls it
+torch::Tensor decode_attn_fp8_fwd_at(torch::Tensor qkv,
+                                     torch::Tensor k_cache,
+                                     torch::Tensor v_cache,
+                                     torch::Tensor k_scale,
+                                     torch::Tensor v_scale,
+                                     torch::Tensor pos, int64_t max_pos,
+                                     double scale, int64_t waves) {
+  return da_checked(qkv, k_cache, v_cache, pos, max_pos, scale, kDaChunk,
+                    k_scale, v_scale, waves);
+}
+
+// k and v of the prefill's qkv [B, T, 3*H*64], quantized into slots
+// 0 .. T-1 of fp8 caches and their scales; every check before the launch
+void kv_cache_fill(torch::Tensor qkv, torch::Tensor k_cache,
+                   torch::Tensor v_cache, torch::Tensor k_scale,
+                   torch::Tensor v_scale) {
+  constexpr int64_t kLimit = (int64_t)1 << 31;
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 &&
+              qkv.dim() == 3 && qkv.is_contiguous(),
+              "kv_cache_fill: qkv must be a contiguous bf16 GPU tensor "
+              "[B, T, 3*H*64]");
+  kv_fp8_check("kv_cache_fill", k_cache, v_cache, k_scale, v_scale,
+               qkv.device());
+  const int64_t B = qkv.size(0), T = qkv.size(1), H = k_cache.size(1),
+                Tmax = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(0) == B && H > 0 &&
+              qkv.size(2) == 3 * H * kDaHs,
+              "kv_cache_fill: qkv is ", qkv.sizes(), ", the caches ",
+              k_cache.sizes());
+  TORCH_CHECK(T <= Tmax, "kv_cache_fill: T = ", T, " exceeds Tmax = ", Tmax);
+  TORCH_CHECK(qkv.numel() < kLimit && k_cache.numel() < kLimit,
+              "kv_cache_fill: 2^31 elements or more in an operand");
+  for (const torch::Tensor* t : {&qkv, &k_cache, &v_cache})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "kv_cache_fill: operands must be 16-byte aligned");
+  if (B == 0 || T == 0) return;
+  const int64_t groups = 2 * B * H * T;  // 4 lanes each, 64 per workgroup
+  hipLaunchKernelGGL(
+      kv_cache_fill_kernel, dim3((unsigned)((groups + 63) / 64)), dim3(256),
+      0, at::hip::getCurrentHIPStream().stream(),
+      reinterpret_cast<const unsigned short*>(qkv.data_ptr()),
+      reinterpret_cast<unsigned char*>(k_cache.data_ptr()),
+      reinterpret_cast<unsigned char*>(v_cache.data_ptr()),
+      k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)B, (int)T,
+      (int)H, (int)Tmax);
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "kv_cache_fill: ", hipGetErrorString(e));
 }
 
 // the same op at another chunk size, for the measurement that picks

@@ -1071,9 +1071,23 @@ bool conv1x1_bwd_data_supported(long cout, long cin);
 long conv1x1_bwd_data_row_tile(long cout, long cin);
 // single-token attention over a KV cache, split along the KV range, with
 // the append of the new k/v row — defined in decode_attn.hip
+// with k_scale / v_scale [B, H, Tmax]: the caches are float8_e4m3fn
 torch::Tensor decode_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
-                              int64_t max_pos, double scale);
+                              int64_t max_pos, double scale,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale);
+torch::Tensor decode_attn_fp8_fwd_at(torch::Tensor qkv,
+                                     torch::Tensor k_cache,
+                                     torch::Tensor v_cache,
+                                     torch::Tensor k_scale,
+                                     torch::Tensor v_scale,
+                                     torch::Tensor pos, int64_t max_pos,
+                                     double scale, int64_t waves);
+// the prefill's quantizing fill of an fp8 KV cache
+void kv_cache_fill(torch::Tensor qkv, torch::Tensor k_cache,
+                   torch::Tensor v_cache, torch::Tensor k_scale,
+                   torch::Tensor v_scale);
 torch::Tensor decode_attn_fwd_at_chunk(torch::Tensor qkv,
                                        torch::Tensor k_cache,
                                        torch::Tensor v_cache,
@@ -1109,7 +1123,9 @@ std::tuple<torch::Tensor, torch::Tensor> decode_layer_fwd(
     torch::Tensor pos, int64_t max_pos, double scale, torch::Tensor proj_w,
     torch::Tensor proj_b, torch::Tensor ln2_w, torch::Tensor ln2_b,
     torch::Tensor fc_w, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
-    torch::Tensor mlp_proj_b, double eps);
+    torch::Tensor mlp_proj_b, double eps,
+    c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale);
 // the same with float8_e4m3fn weights [N, K] and fp32 row scales [N]
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
 skinny_linear_fp8_fwd_at(
@@ -1126,7 +1142,9 @@ std::tuple<torch::Tensor, torch::Tensor> decode_layer_fp8_fwd(
     torch::Tensor proj_w, torch::Tensor proj_s, torch::Tensor proj_b,
     torch::Tensor ln2_w, torch::Tensor ln2_b, torch::Tensor fc_w,
     torch::Tensor fc_s, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
-    torch::Tensor mlp_proj_s, torch::Tensor mlp_proj_b, double eps);
+    torch::Tensor mlp_proj_s, torch::Tensor mlp_proj_b, double eps,
+    c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale);
 // top-k / top-p / Philox token sampling with the decode loop's EOS and
 // output-write epilogue, one launch — defined in sample.hip
 torch::Tensor sample_fwd(torch::Tensor logits, torch::Tensor seeds,
@@ -1339,7 +1357,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "single-token attention over a KV cache (split-KV) + append",
         pybind11::arg("qkv"), pybind11::arg("k_cache"),
         pybind11::arg("v_cache"), pybind11::arg("pos"),
-        pybind11::arg("max_pos"), pybind11::arg("scale"));
+        pybind11::arg("max_pos"), pybind11::arg("scale"),
+        pybind11::arg("k_scale") = c10::optional<torch::Tensor>(),
+        pybind11::arg("v_scale") = c10::optional<torch::Tensor>());
+  m.def("decode_attn_fp8_fwd_at", &decode_attn_fp8_fwd_at,
+        "decode_attn_fwd over an fp8 cache at 2 or 4 waves (measurement)");
+  m.def("kv_cache_fill", &kv_cache_fill,
+        "quantize the prefill's k and v into an fp8 KV cache",
+        pybind11::arg("qkv"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("k_scale"),
+        pybind11::arg("v_scale"));
   m.def("decode_attn_fwd_at_chunk", &decode_attn_fwd_at_chunk,
         "decode_attn_fwd at a chunk size of 64, 128 or 256 (measurement)");
   m.def("decode_attn_chunk", &decode_attn_chunk,
@@ -1363,13 +1390,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "skinny_linear_fwd at (waves, row_tiles) of (4, 1), (8, 1) or "
         "(8, 2) (measurement)");
   m.def("decode_layer_fwd", &decode_layer_fwd,
-        "one GPT-2 block of a decode step: returns (x_mid, mlp_out)");
+        "one GPT-2 block of a decode step: returns (x_mid, mlp_out); the "
+        "last two arguments are an fp8 KV cache's k_scale / v_scale or "
+        "None");
   m.def("skinny_linear_fp8_fwd_at", &skinny_linear_fp8_fwd_at,
         "skinny_linear_fwd with fp8 weights at (row_tiles, wide, uk) "
         "(measurement)");
   m.def("decode_layer_fp8_fwd", &decode_layer_fp8_fwd,
         "decode_layer_fwd with float8_e4m3fn weights, each followed by its "
-        "fp32 row scales");
+        "fp32 row scales; then k_scale / v_scale or None");
   m.def("sample_fwd", &sample_fwd,
         "top-k / top-p / Philox sampling + EOS and output-write epilogue",
         pybind11::arg("logits"), pybind11::arg("seeds"),

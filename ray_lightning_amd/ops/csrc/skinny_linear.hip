@@ -70,7 +70,8 @@
 //
 // decode_layer_fwd enqueues one GPT-2 block of a decode step from one
 // host call: [add + LN1 + c_attn], decode attention (decode_attn.hip, as
-// it stands), [c_proj], [add + LN2 + c_fc + GELU], [c_proj].
+// it stands, over a bf16 cache or, with k_scale / v_scale, an fp8 one),
+// [c_proj], [add + LN2 + c_fc + GELU], [c_proj].
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
@@ -78,10 +79,12 @@
 #include <cmath>
 #include <tuple>
 
-// defined in decode_attn.hip
+// defined in decode_attn.hip; with scales the caches are float8_e4m3fn
 torch::Tensor decode_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
-                              int64_t max_pos, double scale);
+                              int64_t max_pos, double scale,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale);
 
 // fp32 math of this file stays on the scalar-per-lane VALU forms
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
@@ -764,7 +767,8 @@ namespace {
 // Returns (x_mid, mlp_out): the stream after the attention sublayer and
 // the MLP's output, the pair the next block (or the final LayerNorm)
 // takes as (residual, x). The four weights are bf16 when `scales` is null
-// and float8_e4m3fn with scales[0 .. 3] otherwise.
+// and float8_e4m3fn with scales[0 .. 3] otherwise; the caches are bf16, or
+// float8_e4m3fn when k_scale / v_scale [B, H, Tmax] are given.
 std::tuple<torch::Tensor, torch::Tensor> sl_decode_layer(
     const char* who, torch::Tensor x, c10::optional<torch::Tensor> residual,
     torch::Tensor ln1_w, torch::Tensor ln1_b, torch::Tensor attn_w,
@@ -772,9 +776,12 @@ std::tuple<torch::Tensor, torch::Tensor> sl_decode_layer(
     torch::Tensor pos, int64_t max_pos, double scale, torch::Tensor proj_w,
     torch::Tensor proj_b, torch::Tensor ln2_w, torch::Tensor ln2_b,
     torch::Tensor fc_w, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
-    torch::Tensor mlp_proj_b, double eps, const torch::Tensor* scales) {
+    torch::Tensor mlp_proj_b, double eps, const torch::Tensor* scales,
+    c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale) {
   constexpr int64_t kLimit = (int64_t)1 << 31;
   const bool fp8 = scales != nullptr;
+  const bool kv_fp8 = k_scale.has_value();
   OptTensor as, ps, fs, ms;
   if (fp8) as = scales[0], ps = scales[1], fs = scales[2], ms = scales[3];
   // ---- every check first ------------------------------------------------
@@ -800,15 +807,28 @@ std::tuple<torch::Tensor, torch::Tensor> sl_decode_layer(
   TORCH_CHECK(mlp_proj_w.size(0) == C, who, ": the MLP c_proj must be "
               "[C, F]");
   // what decode_attn_fwd will ask of its operands
+  TORCH_CHECK(kv_fp8 == v_scale.has_value(), who,
+              ": k_scale and v_scale come together or not at all");
   for (const torch::Tensor* c : {&k_cache, &v_cache})
     TORCH_CHECK(c->is_cuda() && c->device() == dev &&
-                c->scalar_type() == at::kBFloat16 && c->dim() == 4 &&
-                c->is_contiguous() && c->size(3) == 64 &&
+                c->scalar_type() ==
+                    (kv_fp8 ? at::kFloat8_e4m3fn : at::kBFloat16) &&
+                c->dim() == 4 && c->is_contiguous() && c->size(3) == 64 &&
                 reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0,
                 who, ": k_cache and v_cache must be contiguous, 16-byte "
-                "aligned bf16 [B, H, Tmax, 64] on x's device");
+                "aligned [B, H, Tmax, 64] on x's device, bf16 or, with "
+                "scales, float8_e4m3fn");
   TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), who,
               ": k_cache and v_cache differ in shape");
+  if (kv_fp8)
+    for (const torch::Tensor* sc : {&*k_scale, &*v_scale})
+      TORCH_CHECK(sc->is_cuda() && sc->device() == dev &&
+                  sc->scalar_type() == at::kFloat && sc->dim() == 3 &&
+                  sc->is_contiguous() && sc->size(0) == k_cache.size(0) &&
+                  sc->size(1) == k_cache.size(1) &&
+                  sc->size(2) == k_cache.size(2),
+                  who, ": k_scale and v_scale must be contiguous fp32 "
+                  "[B, H, Tmax] on x's device");
   const int64_t H = k_cache.size(1), Tmax = k_cache.size(2);
   TORCH_CHECK(k_cache.size(0) == B && H > 0 && H * 64 == C, who,
               ": the caches must be [B = ", B, ", H = C / 64 = ", C / 64,
@@ -834,7 +854,8 @@ std::tuple<torch::Tensor, torch::Tensor> sl_decode_layer(
   sl_run(x, residual.has_value() ? &*residual : nullptr,
          residual.has_value() ? &x1 : nullptr, attn_w, as, ab, l1w, l1b, eps,
          false, qkv, sl_split(3 * C, C, fp8));
-  auto att = decode_attn_fwd(qkv, k_cache, v_cache, pos, max_pos, scale);
+  auto att = decode_attn_fwd(qkv, k_cache, v_cache, pos, max_pos, scale,
+                             k_scale, v_scale);
   auto att_out = torch::empty({B, C}, opt);
   sl_run(att, nullptr, nullptr, proj_w, ps, pb, none, none, eps, false,
          att_out, sl_split(C, C, fp8));
@@ -857,11 +878,14 @@ std::tuple<torch::Tensor, torch::Tensor> decode_layer_fwd(
     torch::Tensor pos, int64_t max_pos, double scale, torch::Tensor proj_w,
     torch::Tensor proj_b, torch::Tensor ln2_w, torch::Tensor ln2_b,
     torch::Tensor fc_w, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
-    torch::Tensor mlp_proj_b, double eps) {
+    torch::Tensor mlp_proj_b, double eps,
+    c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale) {
   return sl_decode_layer("decode_layer_fwd", x, residual, ln1_w, ln1_b,
                          attn_w, attn_b, k_cache, v_cache, pos, max_pos,
                          scale, proj_w, proj_b, ln2_w, ln2_b, fc_w, fc_b,
-                         mlp_proj_w, mlp_proj_b, eps, nullptr);
+                         mlp_proj_w, mlp_proj_b, eps, nullptr, k_scale,
+                         v_scale);
 }
 
 // the same block with float8_e4m3fn weights and their fp32 row scales
@@ -873,10 +897,13 @@ std::tuple<torch::Tensor, torch::Tensor> decode_layer_fp8_fwd(
     torch::Tensor proj_w, torch::Tensor proj_s, torch::Tensor proj_b,
     torch::Tensor ln2_w, torch::Tensor ln2_b, torch::Tensor fc_w,
     torch::Tensor fc_s, torch::Tensor fc_b, torch::Tensor mlp_proj_w,
-    torch::Tensor mlp_proj_s, torch::Tensor mlp_proj_b, double eps) {
+    torch::Tensor mlp_proj_s, torch::Tensor mlp_proj_b, double eps,
+    c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale) {
   const torch::Tensor scales[4] = {attn_s, proj_s, fc_s, mlp_proj_s};
   return sl_decode_layer("decode_layer_fp8_fwd", x, residual, ln1_w, ln1_b,
                          attn_w, attn_b, k_cache, v_cache, pos, max_pos,
                          scale, proj_w, proj_b, ln2_w, ln2_b, fc_w, fc_b,
-                         mlp_proj_w, mlp_proj_b, eps, scales);
+                         mlp_proj_w, mlp_proj_b, eps, scales, k_scale,
+                         v_scale);
 }

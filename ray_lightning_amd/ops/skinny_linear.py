@@ -16,7 +16,7 @@ bias and GELU; LayerNorm statistics, the accumulation and GELU are fp32.
 
 ``decode_layer(...)`` is one GPT-2 block of a decode step built from it:
 [add + LN1 + c_attn], ``decode_attention`` over the KV cache (with the
-append), [c_proj], [add + LN2 + c_fc + GELU], [c_proj].
+append; bf16 or, with ``k_scale`` / ``v_scale``, fp8), [c_proj], [add + LN2 + c_fc + GELU], [c_proj].
 
 On the GPU, for bf16 with ``M <= 64``, ``K % 32 == 0`` and fp32 LayerNorm
 parameters, both are the HIP code of csrc/skinny_linear.hip: an MFMA
@@ -220,14 +220,16 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor,
 def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
                  ln1, c_attn, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  pos: torch.Tensor, max_pos: int, attn_proj, ln2, c_fc,
-                 mlp_proj):
+                 mlp_proj, k_scale: Optional[torch.Tensor] = None,
+                 v_scale: Optional[torch.Tensor] = None):
     """One pre-norm GPT-2 block of a decode step. ``x`` [B, C] is the
     previous block's MLP output and ``residual`` the stream it is added
     to; for the first block ``x`` is the stream and ``residual`` is
     ``None``. ``ln1`` / ``ln2`` are the block's LayerNorm modules and
     ``c_attn`` / ``attn_proj`` / ``c_fc`` / ``mlp_proj`` its ``nn.Linear``
     modules; the caches [B, H, Tmax, hs], ``pos`` and ``max_pos`` are
-    ``decode_attention``'s. Returns ``(x_mid, mlp_out)``: the stream after
+    ``decode_attention``'s, ``k_scale`` / ``v_scale`` [B, H, Tmax] included
+    when the caches are float8_e4m3fn (ops/decode_attn.py). Returns ``(x_mid, mlp_out)``: the stream after
     the attention sublayer and the MLP's output, which the next block (or
     the final LayerNorm) takes as ``(residual, x)``."""
     B, C = x.shape
@@ -248,7 +250,8 @@ def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
     # kernel's own gate (RLA_DECODE_ATTN) has to be on as well
     if (_kernel_shape(x, c_attn.weight, ln1.weight) and kernel_enabled()
             and _attn_kernel_enabled()
-            and hs == 64 and k_cache.dtype == torch.bfloat16
+            and hs == 64 and k_cache.dtype == (
+                torch.bfloat16 if k_scale is None else FP8)
             and c_fc.weight.shape[0] % 32 == 0
             and ln2.weight.dtype == torch.float32
             and all(m.bias is not None for m in linears)):
@@ -257,20 +260,22 @@ def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
                 x, residual, ln1.weight, ln1.bias, aw, as_, c_attn.bias,
                 k_cache, v_cache, pos, int(max_pos), 1.0 / math.sqrt(hs),
                 pw, ps, attn_proj.bias, ln2.weight, ln2.bias, fw, fs,
-                c_fc.bias, mw, ms, mlp_proj.bias, float(ln1.eps))
+                c_fc.bias, mw, ms, mlp_proj.bias, float(ln1.eps), k_scale,
+                v_scale)
         return _ext_with("decode_layer_fwd").decode_layer_fwd(
             x, residual, ln1.weight, ln1.bias, c_attn.weight, c_attn.bias,
             k_cache, v_cache, pos, int(max_pos), 1.0 / math.sqrt(hs),
             attn_proj.weight, attn_proj.bias, ln2.weight, ln2.bias,
             c_fc.weight, c_fc.bias, mlp_proj.weight, mlp_proj.bias,
-            float(ln1.eps))
+            float(ln1.eps), k_scale, v_scale)
     ln = dict(ln_weight=ln1.weight, ln_bias=ln1.bias, eps=ln1.eps,
               weight_scale=as_)
     if residual is None:
         qkv, x1 = skinny_linear(x, aw, c_attn.bias, **ln), x
     else:
         qkv, x1 = skinny_linear(x, aw, c_attn.bias, residual=residual, **ln)
-    att = decode_attention(qkv, k_cache, v_cache, pos, max_pos)
+    att = decode_attention(qkv, k_cache, v_cache, pos, max_pos,
+                           k_scale=k_scale, v_scale=v_scale)
     att = skinny_linear(att, pw, attn_proj.bias, weight_scale=ps)
     hid, x_mid = skinny_linear(att, fw, c_fc.bias, residual=x1,
                                ln_weight=ln2.weight, ln_bias=ln2.bias,
