@@ -553,7 +553,8 @@ class GPT2(nn.Module):
         and filled by ``kv_cache_fill`` after the prefill. Every token
         attends the dequantized values, its own included. It needs a bf16
         model with head size 64 (``ValueError`` otherwise); ``prefill_chunk``
-        and ``draft_tokens`` work with it through a torch composition.
+        and ``draft_tokens`` run the append kernel's fp8 variant over it
+        (ops/append_attn.py).
 
         Runs without gradients, in eval mode; the module's mode is put
         back afterwards."""

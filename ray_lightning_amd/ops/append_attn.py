@@ -31,11 +31,17 @@ caches, then a masked softmax in fp32 (on the GPU: SDPA with the same
 mask).
 
 Over an fp8 cache (``k_scale`` / ``v_scale`` given, ops/decode_attn.py) the
-call is a torch composition on the same contract as ``decode_attention``:
-the ``T`` new rows are quantized and stored as codes and scales, the caches
-are dequantized into bf16 temporaries, and the bf16 path above (kernel or
-twin) attends those with the new rows' dequantized values. Correct, not
-fast: the MFMA kernel has no fp8 variant yet.
+contract is ``decode_attention``'s: the ``T`` new rows are quantized as
+``quantize_kv`` does and stored as codes and scales, and query ``t``
+attends the dequantized cache and the dequantized new rows ``0 .. t``:
+attention over the cache as the call leaves it. On the GPU that is the fp8
+variant of the same kernel under the same gate (docs/DESIGN.md §21,
+profiles/append_attn_fp8.md): codes and scales go from global memory to
+registers, ``v_cvt_scalef32_pk_bf16_fp8`` makes them the MFMA's bf16
+operands, and the new rows are quantized, stored and attended as stored in
+the launch. Its twin (``_fp8``: CPU, other shapes, the gate off) is a torch
+composition: ``quantize_kv`` and a byte ``scatter_``, the caches
+dequantized into bf16 temporaries, then the bf16 path above on those.
 """
 from __future__ import annotations
 
@@ -116,8 +122,8 @@ def _twin(qkv, k_cache, v_cache, pos, max_pos):
 
 
 def _fp8(qkv, k_cache, v_cache, k_scale, v_scale, pos, max_pos):
-    """Quantize and store the new rows, then the bf16 op on dequantized
-    temporaries (module docstring)."""
+    """The fp8 kernel's twin: quantize and store the new rows, then the
+    bf16 op on dequantized temporaries (module docstring)."""
     from .decode_attn import dequantize_kv, quantize_kv
     B, H, Tmax, hs = k_cache.shape
     T = qkv.shape[1]
@@ -165,6 +171,19 @@ def append_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
         raise ValueError(f"n_head = {n_head}, the caches hold {H} heads")
     if max_pos is None:
         max_pos = Tmax - (qkv.shape[1] if qkv.dim() == 3 else 1)
+    if _kernel_shape(qkv, k_cache) and _kernel_enabled():
+        ext = _load_ext()
+        if not hasattr(ext, "append_attn_fwd"):
+            raise RuntimeError(
+                "_hip_ops has no append_attn_fwd: rebuild with "
+                "`python -m ray_lightning_amd.ops.build`")
+        # the one checked host path: every other operand check is there
+        if k_scale is not None or v_scale is not None:
+            return ext.append_attn_fwd(qkv, k_cache, v_cache, pos,
+                                       int(max_pos), 1.0 / math.sqrt(hs),
+                                       k_scale, v_scale)
+        return ext.append_attn_fwd(qkv, k_cache, v_cache, pos,
+                                   int(max_pos), 1.0 / math.sqrt(hs))
     from .decode_attn import _check_scales
     _check_scales(k_cache, v_cache, k_scale, v_scale)
     if k_scale is not None:
@@ -183,15 +202,6 @@ def append_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
                 f"does not fit Tmax = {Tmax}")
         return _fp8(qkv.contiguous(), k_cache, v_cache, k_scale, v_scale,
                     pos, int(max_pos))
-    if _kernel_shape(qkv, k_cache) and _kernel_enabled():
-        ext = _load_ext()
-        if not hasattr(ext, "append_attn_fwd"):
-            raise RuntimeError(
-                "_hip_ops has no append_attn_fwd: rebuild with "
-                "`python -m ray_lightning_amd.ops.build`")
-        # the one checked host path: every other operand check is there
-        return ext.append_attn_fwd(qkv, k_cache, v_cache, pos,
-                                   int(max_pos), 1.0 / math.sqrt(hs))
     if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] < 1 \
             or qkv.shape[2] != 3 * H * hs:
         raise ValueError(

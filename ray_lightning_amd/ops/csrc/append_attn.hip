@@ -48,6 +48,28 @@
 //    once with the neutral partial (0, -inf, 0); a chunk wholly below
 //    pos[b] skips the per-element mask.
 //
+// fp8 cache (append_attn_partial_kernel<true>, docs/DESIGN.md §21): K and V
+// are OCP float8_e4m3fn codes with one fp32 power-of-two scale per (b, h,
+// position), [B, H, Tmax]. The geometry, the softmax, the mask, the folds
+// and the combine kernel are the ones above; what differs is how operands
+// reach the MFMA registers and what the append does:
+//  - a cached K row is 64 bytes: lane (row qi, group g) loads one 16-byte
+//    vector, codes 16g .. 16g+15, which feeds both MFMAs of the subtile
+//    (the first 8 codes are kk = 0). Q's B-fragments load the same
+//    permutation, q[16g + 8kk ..];
+//  - a wave's 32 V rows are 2 KiB, two 16-byte loads per lane; the 16 codes
+//    become two bf16 granules of the same swizzled image;
+//  - a load holds one position's codes, so a lane fetches one scale per
+//    load (4 bytes, behind the same kv < pos[b] as the codes), and
+//    v_cvt_scalef32_pk_bf16_fp8 turns two codes into two scaled bf16: the
+//    operands are exactly the dequantized values;
+//  - new rows come from qkv as bf16 in the same element order. The 4 lanes
+//    that share a row take its absmax, form scale and codes as quantize_kv
+//    does (kv_fp8_core.h) and convert the codes back like cached ones, so
+//    every tile attends what tile 0 stores: codes as 16-byte vectors, the
+//    scale from one lane per row. One writer per byte, and neither codes
+//    nor scales at or past pos[b] are read.
+//
 // pos is read on the device only. A row whose pos[b] lies outside
 // [0, max_pos] is inactive: it is replaced by -1 before any use, every
 // chunk is then "above" it, no address is formed from it, nothing is
@@ -57,6 +79,14 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <cmath>
+#include <type_traits>
+
+#include "kv_fp8_core.h"
+
+// what a pair of fp8 caches and their scales must be (decode_attn.hip)
+void kv_fp8_check(const char* who, const torch::Tensor& k_cache,
+                  const torch::Tensor& v_cache, const torch::Tensor& k_scale,
+                  const torch::Tensor& v_scale, const at::Device& dev);
 
 // fp32 math of this file stays on the scalar-per-lane VALU forms
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
@@ -115,10 +145,31 @@ __device__ __forceinline__ bf16x8 aa_read_vt(const char* img, int col16,
   return __builtin_bit_cast(bf16x8, uint4v{r0[0], r0[1], r1[0], r1[1]});
 }
 
+// 8 e4m3 codes (two words, low byte first) times their position's scale,
+// as bf16: v_cvt_scalef32_pk_bf16_fp8 turns two codes into two scaled bf16.
+// The scale is a power of two and a code has 4 significant bits, so the
+// products are exact: the MFMA operands are dequantize_kv's values.
+__device__ __forceinline__ bf16x8 aa_dq8(unsigned w0, unsigned w1,
+                                         float scale) {
+  const auto a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, scale, false);
+  const auto b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, scale, true);
+  const auto c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, scale, false);
+  const auto d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, scale, true);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// FP8: the caches are e4m3 codes with one fp32 scale per position (file
+// header, "fp8 cache"); k_scale / v_scale are not read otherwise.
+template <bool FP8>
+using aa_cache_t = std::conditional_t<FP8, unsigned char, unsigned short>;
+
+template <bool FP8>
 __global__ __launch_bounds__(kAaThreads) void append_attn_partial_kernel(
-    const unsigned short* __restrict__ qkv,  // [B, T, 3*H*64]
-    unsigned short* __restrict__ k_cache,    // [B, H, Tmax, 64]
-    unsigned short* __restrict__ v_cache,    // [B, H, Tmax, 64]
+    const unsigned short* __restrict__ qkv,    // [B, T, 3*H*64]
+    aa_cache_t<FP8>* __restrict__ k_cache,     // [B, H, Tmax, 64]
+    aa_cache_t<FP8>* __restrict__ v_cache,     // [B, H, Tmax, 64]
+    float* __restrict__ k_scale,             // [B, H, Tmax]
+    float* __restrict__ v_scale,             // [B, H, Tmax]
     const int* __restrict__ pos,             // [B]
     float* __restrict__ ws,                  // [B*H, T, gridDim.x, 66]
     int H, int T, int Tmax, int max_pos, float scale_log2e) {
@@ -167,7 +218,9 @@ __global__ __launch_bounds__(kAaThreads) void append_attn_partial_kernel(
   const bool store = t0 == 0;
 
   // ---- all loads first: Q^T, K fragments, the V rows -------------------
-  // Q^T B-fragments: column qi = query t0 + qi, k = 32*kk + 8*g ..
+  // Q^T B-fragments: column qi = query t0 + qi, k = 32*kk + 8*g .. The MFMA
+  // sums over k, so any order of the 64 elements serves as long as K uses
+  // the same one: over an fp8 cache k = 16*g + 8*kk .. (K loads below).
   bf16x8 qf[2];
   {
     const int t = t0 + qi;
@@ -176,66 +229,167 @@ __global__ __launch_bounds__(kAaThreads) void append_attn_partial_kernel(
       qf[kk] = bf16x8{};
       if (t < T)
         qf[kk] = *reinterpret_cast<const bf16x8*>(
-            new_rows + (long)t * 3 * C + kk * 32 + g * 8);
+            new_rows + (long)t * 3 * C +
+            (FP8 ? g * 16 + kk * 8 : kk * 32 + g * 8));
     }
   }
-  // K A-fragments: row qi of subtile s is position kv0 + 32*wave + 16*s +
-  // qi, k = 32*kk + 8*g ..
   bf16x8 kraw[2][2];
-  #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int kv = kv0 + wave * kAaWaveKv + s * 16 + qi;
-    #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int e = kk * 32 + g * 8;
-      kraw[s][kk] = bf16x8{};
-      if (kv <= hi) {
-        const unsigned short* a =
-            kv < p ? k_cache + cache_row + (long)kv * kAaHs + e
-                   : new_rows + (long)(kv - p) * 3 * C + C + e;
-        kraw[s][kk] = *reinterpret_cast<const bf16x8*>(a);
-      }
-    }
-  }
-  // V rows, row-major: row 8*i + (lane >> 3) of the wave, granule lane & 7
-  bf16x8 vraw[4];
-  #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int kv = kv0 + wave * kAaWaveKv + i * 8 + (lane >> 3);
-    const int e = (lane & 7) * 8;
-    vraw[i] = bf16x8{};
-    if (kv <= hi) {
-      const unsigned short* a =
-          kv < p ? v_cache + cache_row + (long)kv * kAaHs + e
-                 : new_rows + (long)(kv - p) * 3 * C + 2 * C + e;
-      vraw[i] = *reinterpret_cast<const bf16x8*>(a);
-    }
-  }
-
-  // ---- the append (tile 0), and V into the wave's LDS image ------------
-  if (store) {
+  if constexpr (!FP8) {
+    // K A-fragments: row qi of subtile s is position kv0 + 32*wave + 16*s +
+    // qi, k = 32*kk + 8*g ..
     #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int kv = kv0 + wave * kAaWaveKv + s * 16 + qi;
       #pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        if (kv >= p && kv <= hi)  // p <= kv <= p + T - 1 < Tmax
-          *reinterpret_cast<bf16x8*>(k_cache + cache_row +
-                                     (long)kv * kAaHs + kk * 32 + g * 8) =
-              kraw[s][kk];
+      for (int kk = 0; kk < 2; ++kk) {
+        const int e = kk * 32 + g * 8;
+        kraw[s][kk] = bf16x8{};
+        if (kv <= hi) {
+          const unsigned short* a =
+              kv < p ? k_cache + cache_row + (long)kv * kAaHs + e
+                     : new_rows + (long)(kv - p) * 3 * C + C + e;
+          kraw[s][kk] = *reinterpret_cast<const bf16x8*>(a);
+        }
+      }
     }
+    // V rows, row-major: row 8*i + (lane >> 3) of the wave, granule lane & 7
+    bf16x8 vraw[4];
     #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int kv = kv0 + wave * kAaWaveKv + i * 8 + (lane >> 3);
-      if (kv >= p && kv <= hi)
-        *reinterpret_cast<bf16x8*>(v_cache + cache_row + (long)kv * kAaHs +
-                                   (lane & 7) * 8) = vraw[i];
+      const int e = (lane & 7) * 8;
+      vraw[i] = bf16x8{};
+      if (kv <= hi) {
+        const unsigned short* a =
+            kv < p ? v_cache + cache_row + (long)kv * kAaHs + e
+                   : new_rows + (long)(kv - p) * 3 * C + 2 * C + e;
+        vraw[i] = *reinterpret_cast<const bf16x8*>(a);
+      }
+    }
+
+    // ---- the append (tile 0), and V into the wave's LDS image ------------
+    if (store) {
+      #pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int kv = kv0 + wave * kAaWaveKv + s * 16 + qi;
+        #pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+          if (kv >= p && kv <= hi)  // p <= kv <= p + T - 1 < Tmax
+            *reinterpret_cast<bf16x8*>(k_cache + cache_row +
+                                       (long)kv * kAaHs + kk * 32 + g * 8) =
+                kraw[s][kk];
+      }
+      #pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int kv = kv0 + wave * kAaWaveKv + i * 8 + (lane >> 3);
+        if (kv >= p && kv <= hi)
+          *reinterpret_cast<bf16x8*>(v_cache + cache_row + (long)kv * kAaHs +
+                                     (lane & 7) * 8) = vraw[i];
+      }
+    }
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<bf16x8*>(
+          lds_v[wave] + aa_swz(i * 8 + (lane >> 3), lane & 7)) = vraw[i];
+  } else {
+    // ---- fp8 cache: codes and scales in, bf16 operands out ---------------
+    // K: row qi of subtile s, one 16-byte load of codes 16*g .. 16*g+15 that
+    // feeds both MFMAs of the subtile (the first 8 are kk = 0). V: row
+    // 16*i + (lane >> 2) of the wave, codes 16*(lane & 3) .. Every load
+    // holds one position's codes, so a lane needs one scale per load, behind
+    // the same kv < p as the codes.
+    const long scale_row = (long)bh * Tmax;
+    const int vrow = lane >> 2, vsub = lane & 3;
+    uint4 kc[2], vc[2];
+    float ksc[2], vsc[2];
+    #pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int kv = kv0 + wave * kAaWaveKv + s * 16 + qi;
+      kc[s] = uint4{};
+      ksc[s] = 1.f;
+      if (kv < p) {
+        kc[s] = *reinterpret_cast<const uint4*>(k_cache + cache_row +
+                                                (long)kv * kAaHs + g * 16);
+        ksc[s] = k_scale[scale_row + kv];
+      }
+    }
+    #pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int kv = kv0 + wave * kAaWaveKv + i * 16 + vrow;
+      vc[i] = uint4{};
+      vsc[i] = 1.f;
+      if (kv < p) {
+        vc[i] = *reinterpret_cast<const uint4*>(v_cache + cache_row +
+                                                (long)kv * kAaHs + vsub * 16);
+        vsc[i] = v_scale[scale_row + kv];
+      }
+    }
+    // New rows (uniform: a chunk wholly below p holds none): bf16 from qkv
+    // in the same element order, quantized as quantize_kv does. The 4 lanes
+    // of a K row are 16 and 32 apart, those of a V row adjacent; every lane
+    // runs the absmax shuffles. Every tile attends the codes tile 0 stores.
+    if (kv0 + kAaChunk > p) {
+      #pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int kv = kv0 + wave * kAaWaveKv + s * 16 + qi;
+        const bool fresh = kv >= p && kv <= hi;  // p <= kv <= p + T - 1 < Tmax
+        uint4 a{}, c{};
+        if (fresh) {
+          const unsigned short* src =
+              new_rows + (long)(kv - p) * 3 * C + C + g * 16;
+          a = *reinterpret_cast<const uint4*>(src);
+          c = *reinterpret_cast<const uint4*>(src + 8);
+        }
+        const unsigned amax = kv_row_amax(a, c, 16);
+        if (fresh) {
+          kc[s] = kv_quant_row(a, c, amax);
+          ksc[s] = __builtin_bit_cast(float, kv_scale_bits(amax));
+          if (store) {
+            *reinterpret_cast<uint4*>(k_cache + cache_row + (long)kv * kAaHs +
+                                      g * 16) = kc[s];
+            if (g == 0) k_scale[scale_row + kv] = ksc[s];
+          }
+        }
+      }
+      #pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int kv = kv0 + wave * kAaWaveKv + i * 16 + vrow;
+        const bool fresh = kv >= p && kv <= hi;
+        uint4 a{}, c{};
+        if (fresh) {
+          const unsigned short* src =
+              new_rows + (long)(kv - p) * 3 * C + 2 * C + vsub * 16;
+          a = *reinterpret_cast<const uint4*>(src);
+          c = *reinterpret_cast<const uint4*>(src + 8);
+        }
+        const unsigned amax = kv_row_amax(a, c);
+        if (fresh) {
+          vc[i] = kv_quant_row(a, c, amax);
+          vsc[i] = __builtin_bit_cast(float, kv_scale_bits(amax));
+          if (store) {
+            *reinterpret_cast<uint4*>(v_cache + cache_row + (long)kv * kAaHs +
+                                      vsub * 16) = vc[i];
+            if (vsub == 0) v_scale[scale_row + kv] = vsc[i];
+          }
+        }
+      }
+    }
+    // codes times scale in registers: K into the A-fragments, V as the two
+    // bf16 granules 2*vsub, 2*vsub+1 of its row in the wave's image
+    #pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      kraw[s][0] = aa_dq8(kc[s].x, kc[s].y, ksc[s]);
+      kraw[s][1] = aa_dq8(kc[s].z, kc[s].w, ksc[s]);
+    }
+    #pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      char* img = lds_v[wave];
+      *reinterpret_cast<bf16x8*>(img + aa_swz(i * 16 + vrow, 2 * vsub)) =
+          aa_dq8(vc[i].x, vc[i].y, vsc[i]);
+      *reinterpret_cast<bf16x8*>(img + aa_swz(i * 16 + vrow, 2 * vsub + 1)) =
+          aa_dq8(vc[i].z, vc[i].w, vsc[i]);
     }
   }
-  #pragma unroll
-  for (int i = 0; i < 4; ++i)
-    *reinterpret_cast<bf16x8*>(
-        lds_v[wave] + aa_swz(i * 8 + (lane >> 3), lane & 7)) = vraw[i];
   __syncthreads();
 
   // ---- S^T = K . Q^T: st[s][r] is position kv0 + 32*wave + 16*s + 4*g +
@@ -374,18 +528,28 @@ __global__ __launch_bounds__(kAaHs) void append_attn_combine_kernel(
 long append_attn_chunk() { return kAaChunk; }
 
 // every check happens here, before anything is allocated or launched
+// With scales the caches are fp8.
 torch::Tensor append_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
-                              int64_t max_pos, double scale) {
+                              int64_t max_pos, double scale,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale) {
   constexpr int64_t kLimit = (int64_t)1 << 31;
+  const bool fp8 = k_scale.has_value();
+  TORCH_CHECK(fp8 == v_scale.has_value(),
+              "append_attn_fwd: k_scale and v_scale come together or not "
+              "at all");
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 &&
               qkv.dim() == 3 && qkv.is_contiguous(),
               "append_attn_fwd: qkv must be a contiguous bf16 GPU tensor "
               "[B, T, 3*H*64]");
+  if (fp8)
+    kv_fp8_check("append_attn_fwd", k_cache, v_cache, *k_scale, *v_scale,
+                 qkv.device());
   for (const torch::Tensor* c : {&k_cache, &v_cache})
-    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() &&
-                c->scalar_type() == at::kBFloat16 && c->dim() == 4 &&
-                c->is_contiguous() && c->size(3) == kAaHs,
+    TORCH_CHECK(fp8 || (c->is_cuda() && c->device() == qkv.device() &&
+                        c->scalar_type() == at::kBFloat16 && c->dim() == 4 &&
+                        c->is_contiguous() && c->size(3) == kAaHs),
                 "append_attn_fwd: k_cache and v_cache must be contiguous "
                 "bf16 [B, H, Tmax, 64] on qkv's device");
   TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
@@ -426,15 +590,25 @@ torch::Tensor append_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                          qkv.options().dtype(at::kFloat));
   const float scale_log2e = (float)(scale * 1.4426950408889634);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  hipLaunchKernelGGL(
-      append_attn_partial_kernel,
-      dim3((unsigned)n_chunks, (unsigned)q_tiles, (unsigned)(B * H)),
-      dim3(kAaThreads), 0, stream,
-      reinterpret_cast<const unsigned short*>(qkv.data_ptr()),
-      reinterpret_cast<unsigned short*>(k_cache.data_ptr()),
-      reinterpret_cast<unsigned short*>(v_cache.data_ptr()),
-      pos.data_ptr<int>(), ws.data_ptr<float>(), (int)H, (int)T, (int)Tmax,
-      (int)max_pos, scale_log2e);
+  const dim3 grid((unsigned)n_chunks, (unsigned)q_tiles, (unsigned)(B * H));
+  if (fp8)
+    hipLaunchKernelGGL(
+        append_attn_partial_kernel<true>, grid, dim3(kAaThreads), 0, stream,
+        reinterpret_cast<const unsigned short*>(qkv.data_ptr()),
+        reinterpret_cast<unsigned char*>(k_cache.data_ptr()),
+        reinterpret_cast<unsigned char*>(v_cache.data_ptr()),
+        k_scale->data_ptr<float>(), v_scale->data_ptr<float>(),
+        pos.data_ptr<int>(), ws.data_ptr<float>(), (int)H, (int)T, (int)Tmax,
+        (int)max_pos, scale_log2e);
+  else
+    hipLaunchKernelGGL(
+        append_attn_partial_kernel<false>, grid, dim3(kAaThreads), 0, stream,
+        reinterpret_cast<const unsigned short*>(qkv.data_ptr()),
+        reinterpret_cast<unsigned short*>(k_cache.data_ptr()),
+        reinterpret_cast<unsigned short*>(v_cache.data_ptr()),
+        (float*)nullptr, (float*)nullptr, pos.data_ptr<int>(),
+        ws.data_ptr<float>(), (int)H, (int)T, (int)Tmax, (int)max_pos,
+        scale_log2e);
   hipLaunchKernelGGL(append_attn_combine_kernel,
                      dim3((unsigned)T, (unsigned)(B * H)), dim3(kAaHs), 0,
                      stream, ws.data_ptr<float>(),

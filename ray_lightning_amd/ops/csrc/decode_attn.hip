@@ -279,52 +279,8 @@ __device__ __forceinline__ void fp8x16_to_float(const uint4& raw, float* f) {
   fp8x4_to_float(raw.w, f + 12);
 }
 
-// largest |x| of 16 bf16 values, as fp32 bits (non-finite values sort on
-// top, which is what kv_scale_bits wants)
-__device__ __forceinline__ unsigned kv_amax16(const uint4& a, const uint4& b) {
-  const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  unsigned m = 0;
-  #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    m = max(m, (w[i] << 16) & 0x7fff0000u);
-    m = max(m, w[i] & 0x7fff0000u);
-  }
-  return m;
-}
-
-// 16 bf16 values as 16 e4m3 codes under scale 2^(se - 127), low byte first
-__device__ __forceinline__ uint4 kv_quant16(const uint4& a, const uint4& b,
-                                            int se) {
-  const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  unsigned o[4];
-  #pragma unroll
-  for (int i = 0; i < 4; ++i)
-    o[i] = kv_quant(w[2 * i] & 0xffffu, se) |
-           kv_quant(w[2 * i] >> 16, se) << 8 |
-           kv_quant(w[2 * i + 1] & 0xffffu, se) << 16 |
-           kv_quant(w[2 * i + 1] >> 16, se) << 24;
-  return uint4{o[0], o[1], o[2], o[3]};
-}
-
-// A row of 64 bf16 is held by 4 adjacent lanes, 16 values each (a, b).
-// Its absmax as fp32 bits; every lane of the wave runs the shuffles.
-__device__ __forceinline__ unsigned kv_row_amax(const uint4& a,
-                                                const uint4& b) {
-  unsigned amax = kv_amax16(a, b);
-  amax = max(amax, (unsigned)__shfl_xor((int)amax, 1, 64));
-  amax = max(amax, (unsigned)__shfl_xor((int)amax, 2, 64));
-  return amax;
-}
-
-// This lane's 16 codes of the row with that absmax. A zero row has scale 1
-// (its codes are signed zeros); a non-finite one gets the NaN code next to
-// its NaN scale.
-__device__ __forceinline__ uint4 kv_quant_row(const uint4& a, const uint4& b,
-                                              unsigned amax) {
-  if (amax >= 0x7f800000u)
-    return uint4{0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu};
-  return kv_quant16(a, b, amax == 0 ? 127 : kv_scale_exp(amax));
-}
+// kv_amax16, kv_row_amax and kv_quant_row (a row of 64 bf16 on 4 adjacent
+// lanes) are in kv_fp8_core.h.
 
 // The partial kernel over an fp8 cache: the grid, the chunk partition, the
 // partial's layout and the folds are decode_attn_partial_kernel's, so the
@@ -602,7 +558,10 @@ void da_fp8_launch(const torch::Tensor& qkv, torch::Tensor& k_cache,
   TORCH_CHECK(e == hipSuccess, "decode_attn_fwd: ", hipGetErrorString(e));
 }
 
-// what a pair of fp8 caches and their scales must be, for `who`
+}  // namespace
+
+// what a pair of fp8 caches and their scales must be, for `who`; also the
+// check of append_attn.hip
 void kv_fp8_check(const char* who, const torch::Tensor& k_cache,
                   const torch::Tensor& v_cache, const torch::Tensor& k_scale,
                   const torch::Tensor& v_scale, const at::Device& dev) {
@@ -623,6 +582,8 @@ void kv_fp8_check(const char* who, const torch::Tensor& k_cache,
                 who, ": k_scale and v_scale must be contiguous fp32 "
                 "[B, H, Tmax] on qkv's device");
 }
+
+namespace {
 
 template <int CHUNK>
 void da_launch(const torch::Tensor& qkv, torch::Tensor& k_cache,

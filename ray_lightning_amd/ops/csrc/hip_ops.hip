@@ -1096,9 +1096,12 @@ torch::Tensor decode_attn_fwd_at_chunk(torch::Tensor qkv,
 long decode_attn_chunk();
 // T new tokens per row over a KV cache: MFMA split-KV kernel with the
 // append of the T k/v rows — defined in append_attn.hip
+// with k_scale / v_scale [B, H, Tmax]: the caches are float8_e4m3fn
 torch::Tensor append_attn_fwd(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor pos,
-                              int64_t max_pos, double scale);
+                              int64_t max_pos, double scale,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale);
 long append_attn_chunk();
 // linear layers of a decode step (M <= 64 rows): MFMA weight stream with
 // LayerNorm / residual add in the prologue and bias / GELU in the epilogue,
@@ -1375,7 +1378,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "T-token attention over a KV cache (MFMA split-KV) + append",
         pybind11::arg("qkv"), pybind11::arg("k_cache"),
         pybind11::arg("v_cache"), pybind11::arg("pos"),
-        pybind11::arg("max_pos"), pybind11::arg("scale"));
+        pybind11::arg("max_pos"), pybind11::arg("scale"),
+        pybind11::arg("k_scale") = c10::optional<torch::Tensor>(),
+        pybind11::arg("v_scale") = c10::optional<torch::Tensor>());
   m.def("append_attn_chunk", &append_attn_chunk,
         "KV positions per workgroup of append_attn_fwd");
   m.def("skinny_linear_fwd", &skinny_linear_fwd,

@@ -1,5 +1,6 @@
 // The KV cache's fp8 format in integer arithmetic, shared by the decode
-// kernel's append and the fill kernel of decode_attn.hip. docs/DESIGN.md
+// kernel's append and the fill kernel of decode_attn.hip and by the append
+// kernel of append_attn.hip. docs/DESIGN.md
 // §20 has the contract; in short, for a row x[0 .. 63] of bf16:
 //
 //   scale = 2^ceil(log2(absmax / 448)), 1 for an all-zero row
@@ -79,3 +80,56 @@ KV_HD unsigned kv_quant(unsigned x, int se) {
   // the next exponent by plain addition
   return sign | (unsigned)(base + (int)r);
 }
+
+#if defined(__HIPCC__)
+// ---- a row of 64 bf16 held by 4 lanes, 16 values each (two uint4 a, b):
+// the layout of the decode kernel's append, the fill kernel and the append
+// kernel's new rows ------------------------------------------------------
+
+// largest |x| of 16 bf16 values, as fp32 bits (non-finite values sort on
+// top, which is what kv_scale_bits wants)
+__device__ __forceinline__ unsigned kv_amax16(const uint4& a, const uint4& b) {
+  const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  unsigned m = 0;
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    m = max(m, (w[i] << 16) & 0x7fff0000u);
+    m = max(m, w[i] & 0x7fff0000u);
+  }
+  return m;
+}
+
+// 16 bf16 values as 16 e4m3 codes under scale 2^(se - 127), low byte first
+__device__ __forceinline__ uint4 kv_quant16(const uint4& a, const uint4& b,
+                                            int se) {
+  const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  unsigned o[4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i)
+    o[i] = kv_quant(w[2 * i] & 0xffffu, se) |
+           kv_quant(w[2 * i] >> 16, se) << 8 |
+           kv_quant(w[2 * i + 1] & 0xffffu, se) << 16 |
+           kv_quant(w[2 * i + 1] >> 16, se) << 24;
+  return uint4{o[0], o[1], o[2], o[3]};
+}
+
+// The row's absmax as fp32 bits. Its 4 lanes are `stride` and 2 * `stride`
+// apart (1: adjacent lanes); every lane of the wave runs the shuffles.
+__device__ __forceinline__ unsigned kv_row_amax(const uint4& a, const uint4& b,
+                                                int stride = 1) {
+  unsigned amax = kv_amax16(a, b);
+  amax = max(amax, (unsigned)__shfl_xor((int)amax, stride, 64));
+  amax = max(amax, (unsigned)__shfl_xor((int)amax, 2 * stride, 64));
+  return amax;
+}
+
+// This lane's 16 codes of the row with that absmax. A zero row has scale 1
+// (its codes are signed zeros); a non-finite one gets the NaN code next to
+// its NaN scale.
+__device__ __forceinline__ uint4 kv_quant_row(const uint4& a, const uint4& b,
+                                              unsigned amax) {
+  if (amax >= 0x7f800000u)
+    return uint4{0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu};
+  return kv_quant16(a, b, amax == 0 ? 127 : kv_scale_exp(amax));
+}
+#endif

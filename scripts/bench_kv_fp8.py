@@ -20,6 +20,20 @@ a GPU and the built extension.
 (d) The largest logit difference between an fp8-cache and a bf16-cache
     greedy run of the test model (2 layers, 2 heads, n_embd 128) on random
     weights, over the steps before their tokens first differ.
+(e) Append attention over an fp8 cache (profiles/append_attn_fp8.md), at
+    the points of profiles/append_attn.md: B=8, H=25, Tmax=1024, pos in
+    {128, 512, 960}, T in {4, 16, 64}. Contestants: the fp8 append kernel,
+    the ``_fp8`` torch composition it replaces (quantize and scatter with
+    ATen, dequantize both caches, the bf16 append kernel on the copies),
+    and the bf16 append kernel on a bf16 cache. Rule, fixed before the run:
+    the kernel is the default over an fp8 cache iff at all nine points its
+    median is below the composition's by more than the larger of the two
+    spreads.
+(f) GPT-2-XL, fp8 weights, RLA_SKINNY_LINEAR=1, fp8 cache: one extend
+    forward to the last token's logits, with the kernel and with the
+    composition: a 64-token turn on 512 cached tokens at B=8, and a
+    spec-decode step's forward (T = 7) on 256 cached tokens at B=8 and
+    B=64; peak allocated memory of the call.
 """
 import argparse
 import json
@@ -33,6 +47,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ray_lightning_amd import ops  # noqa: E402
+from ray_lightning_amd.ops import append_attn as aa  # noqa: E402
 from ray_lightning_amd.ops import decode_attn as da  # noqa: E402
 
 HBM_MEASURED = 6.29e12
@@ -204,12 +219,118 @@ def logit_difference():
             "tokens_agree": float(same.float().mean())}
 
 
+_APPEND = aa.append_attention
+
+
+def composition(qkv, k8, v8, pos, max_pos, n_head=None, k_scale=None,
+                v_scale=None):
+    """append_attention as it was before the fp8 append kernel: fp8 calls
+    go to the ``_fp8`` composition, whose bf16 call comes back here."""
+    if k_scale is None:
+        return _APPEND(qkv, k8, v8, pos, max_pos, n_head)
+    return aa._fp8(qkv.contiguous(), k8, v8, k_scale, v_scale, pos,
+                   int(max_pos))
+
+
+def append_point(B, H, Tmax, pos, T, window, rounds):
+    g = torch.Generator(device="cuda").manual_seed(pos + T)
+    qkv = torch.randn(B, T, 3 * H * HS, device="cuda", generator=g).bfloat16()
+    ring = []
+    for _ in range(LAYERS):
+        k = torch.randn(B, H, Tmax, HS, device="cuda", generator=g).bfloat16()
+        v = torch.randn(B, H, Tmax, HS, device="cuda", generator=g).bfloat16()
+        ring.append((k, v) + da.quantize_kv(k) + da.quantize_kv(v))
+    pos_t = torch.full((B,), pos, dtype=torch.int32, device="cuda")
+
+    def bf16(i):
+        k, v = ring[i % LAYERS][:2]
+        return aa.append_attention(qkv, k, v, pos_t, pos)
+
+    def fp8(i):
+        _, _, k8, ks, v8, vs = ring[i % LAYERS]
+        return aa.append_attention(qkv, k8, v8, pos_t, pos, k_scale=ks,
+                                   v_scale=vs)
+
+    def composed(i):
+        _, _, k8, ks, v8, vs = ring[i % LAYERS]
+        return composition(qkv, k8, v8, pos_t, pos, None, ks, vs)
+
+    fns = {"fp8_kernel": fp8, "fp8_composition": composed, "bf16_kernel": bf16}
+    res = {"B": B, "pos": pos, "T": T,
+           "kernel_vs_composition_max_abs_diff":
+               (fp8(0).float() - composed(0).float()).abs().max().item()}
+    res.update(alternate(fns, window, rounds))
+    spread = lambda r: r["max_us"] - r["min_us"]
+    k, c = res["fp8_kernel"], res["fp8_composition"]
+    res["kernel_wins"] = c["median_us"] - k["median_us"] > \
+        max(spread(k), spread(c))
+    return res
+
+
+def xl_append(rounds):
+    from ray_lightning_amd.models.gpt2 import (GPT2, GPT2Config,
+                                               to_bf16_training)
+    os.environ["RLA_SKINNY_LINEAR"] = "1"
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        model = GPT2(GPT2Config.gpt2_xl())
+    model = to_bf16_training(model).eval()
+    model.quantize_weights_fp8()
+    cfg = model.cfg
+    out = []
+    for B, P, T in ((8, 512, 64), (8, 256, 7), (64, 256, 7)):
+        idx = torch.randint(0, cfg.vocab_size, (B, P + T), device="cuda")
+        full = torch.full((B,), P, dtype=torch.int32, device="cuda")
+        cache = da.KVCache(cfg.n_layer, B, cfg.n_head, 1024, HS, da.FP8,
+                           "cuda")
+        with torch.no_grad():
+            model._hidden(idx[:, :P], None, cache)
+
+        def run(op):
+            aa.append_attention = op
+            cache.set_lengths(full, P)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                h = model._hidden(idx[:, P:], None, cache, True)
+                logits = model.lm_head(h[:, -1]).float()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0, torch.cuda.max_memory_allocated(),
+                    logits)
+
+        ops_ = {"kernel": _APPEND, "composition": composition}
+        res = {"B": B, "cached": P, "T": T}
+        try:
+            last = {n: run(op)[2] for n, op in ops_.items()}   # warm-up
+            t = {n: [] for n in ops_}
+            peak = {}
+            for _ in range(rounds):
+                for n, op in ops_.items():
+                    s, peak[n], _ = run(op)
+                    t[n].append(s)
+        finally:
+            aa.append_attention = _APPEND
+        for n in ops_:
+            res[n] = {"median_ms": 1e3 * statistics.median(t[n]),
+                      "min_ms": 1e3 * min(t[n]), "max_ms": 1e3 * max(t[n]),
+                      "peak_GiB": peak[n] / 2 ** 30}
+        res["last_logits_max_abs_diff"] = \
+            (last["kernel"] - last["composition"]).abs().max().item()
+        print("#", json.dumps(res), flush=True)
+        out.append(res)
+        del cache
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.25,
                     help="seconds of device time per sample")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--append-only", action="store_true",
+                    help="sections (e) and (f) only")
     args = ap.parse_args()
     ext = ops._load_ext() if torch.cuda.is_available() else None
     if ext is None or not hasattr(ext, "decode_attn_fp8_fwd_at"):
@@ -217,6 +338,18 @@ def main():
     os.environ["RLA_DECODE_ATTN"] = "1"
     out = {"kernel": [], "fill": [], "hip": torch.version.hip,
            "rounds": args.rounds, "window_s": args.window}
+    out["append"] = []
+    for pos in (128, 512, 960):
+        for T in (4, 16, 64):
+            r = append_point(8, 25, 1024, pos, T, args.window, args.rounds)
+            out["append"].append(r)
+            print("#", json.dumps(r), flush=True)
+    out["append_default_on"] = all(r["kernel_wins"] for r in out["append"])
+    if not args.skip_model:
+        out["xl_append"] = xl_append(args.rounds)
+    if args.append_only:
+        print(json.dumps(out))
+        return
     for B in (8, 64):
         for pos in (128, 512, 1023):
             r = kernel_point(ext, B, 25, 1024, pos, args.window, args.rounds)
