@@ -120,7 +120,7 @@ class GPT2LM(LightningModule):
                  gen_eos_id: Optional[int] = None,
                  gen_top_p: Optional[float] = None,
                  gen_seed=None, *, gen_draft_tokens: int = 0,
-                 gen_draft_ngram: int = 3, gen_fp8_weights: bool = False,
+                 gen_draft_ngram: int = 3, gen_fp8_weights=False,
                  gen_fp8_kv: bool = False):
         super().__init__()
         self.save_hyperparameters()
@@ -134,7 +134,8 @@ class GPT2LM(LightningModule):
         self.gen_draft_tokens = gen_draft_tokens
         self.gen_draft_ngram = gen_draft_ngram
         # weight-only fp8 for decode steps (GPT2.quantize_weights_fp8),
-        # applied once, before the first predict_step
+        # applied once, before the first predict_step; "drop" also frees
+        # the bf16 copies (drop_bf16=True: every phase reads the fp8 pair)
         self.gen_fp8_weights = gen_fp8_weights
         self._fp8_quantized = False
         # fp8 KV cache for predict_step (GPT2.generate(kv_fp8=True))
@@ -192,7 +193,8 @@ class GPT2LM(LightningModule):
         else:
             idx = batch
         if self.gen_fp8_weights and not self._fp8_quantized:
-            self.model.eval().quantize_weights_fp8()
+            self.model.eval().quantize_weights_fp8(
+                drop_bf16=self.gen_fp8_weights == "drop")
             self._fp8_quantized = True
         return self.model.generate(
             idx, self.gen_max_new_tokens, prompt_lens=prompt_lens,

@@ -32,7 +32,10 @@ next turn of a conversation, a slice of a chunked prefill
 with at most 64 rows runs every block as one ``decode_layer`` call and
 the final LayerNorm with the LM head as one ``skinny_linear`` call
 (ops/skinny_linear.py). After ``GPT2.quantize_weights_fp8()`` those decode
-steps stream the blocks' linear weights as fp8 (``RLA_SKINNY_FP8``).
+steps stream the blocks' linear weights as fp8 (``RLA_SKINNY_FP8``), and
+after ``quantize_weights_fp8(drop_bf16=True)`` the blocks keep the fp8
+pairs only: prefill, ``extend`` and decode apply them through
+``fp8_linear`` (ops/fp8_linear.py, docs/DESIGN.md §22).
 ``generate(kv_fp8=True)`` keeps the KV cache in fp8 (ops/decode_attn.py,
 docs/DESIGN.md §20).
 """
@@ -86,6 +89,23 @@ class GPT2Config:
         return cls(n_embd=1600, n_layer=48, n_head=25)
 
 
+def linear_dropped(lin: nn.Linear) -> bool:
+    """Whether ``quantize_weights_fp8(drop_bf16=True)`` left ``lin`` with
+    its fp8 pair only: an empty ``weight`` next to ``weight_fp8``."""
+    return lin.weight.numel() == 0 and \
+        getattr(lin, "weight_fp8", None) is not None
+
+
+def _apply_linear(lin: nn.Linear, x, gelu: bool = False):
+    """``lin(x)``, through ``fp8_linear`` (ops/fp8_linear.py) when the bf16
+    weight was dropped; ``gelu`` is for dropped linears only."""
+    if linear_dropped(lin):
+        from ..ops.fp8_linear import fp8_linear
+        return fp8_linear(x, lin.weight_fp8, lin.weight_scale, lin.bias,
+                          gelu=gelu)
+    return lin(x)
+
+
 class CausalSelfAttention(nn.Module):
     def __init__(self, cfg: GPT2Config):
         super().__init__()
@@ -105,7 +125,7 @@ class CausalSelfAttention(nn.Module):
         fp8 cache's layer is ``(k_cache, v_cache, kv, k_scale, v_scale)``
         and is filled by ``kv_cache_fill``."""
         B, T, C = x.shape
-        qkv = self.c_attn(x)
+        qkv = _apply_linear(self.c_attn, x)
         scales = {}
         if cache is not None and len(cache) == 5:
             scales = dict(k_scale=cache[3], v_scale=cache[4])
@@ -115,13 +135,13 @@ class CausalSelfAttention(nn.Module):
             k_cache, v_cache, kv = cache
             y = append_attention(qkv, k_cache, v_cache, kv.pos, kv.max_pos,
                                  self.n_head, **scales)
-            return self.c_proj(y)
+            return _apply_linear(self.c_proj, y)
         if cache is not None and cache[2].prefilled:
             from ..ops.decode_attn import decode_attention
             k_cache, v_cache, kv = cache
             y = decode_attention(qkv.view(B, 3 * C), k_cache, v_cache,
                                  kv.pos, kv.max_pos, self.n_head, **scales)
-            return self.c_proj(y.view(B, 1, C))
+            return _apply_linear(self.c_proj, y.view(B, 1, C))
         if scales:
             from ..ops.decode_attn import kv_cache_fill
             kv_cache_fill(qkv, cache[0], cache[1], **scales)
@@ -143,13 +163,15 @@ class CausalSelfAttention(nn.Module):
                                       flash_attention_qkvpacked)
         p = self.attn_pdrop if self.training else 0.0
         if doc_ids is None:
-            return self.c_proj(
+            return _apply_linear(
+                self.c_proj,
                 flash_attention_qkvpacked(qkv, self.n_head, dropout_p=p))
         hs = C // self.n_head
         q, k, v = (t.view(B, T, self.n_head, hs).transpose(1, 2)
                    for t in qkv.split(C, dim=2))
         y = flash_attention(q, k, v, dropout_p=p, doc_ids=doc_ids)
-        return self.c_proj(y.transpose(1, 2).contiguous().view(B, T, C))
+        return _apply_linear(
+            self.c_proj, y.transpose(1, 2).contiguous().view(B, T, C))
 
 
 class MLP(nn.Module):
@@ -163,6 +185,11 @@ class MLP(nn.Module):
         # the hipBLASLt-epilogue variant stays opt-in via RLA_LT_MLP=1
         # (measured slower on this library build — ops/lt_mlp.py)
         import os
+        if linear_dropped(self.c_fc):
+            # fp8 weights only (inference): GELU in the first call's
+            # epilogue, not the training-only fused_mlp
+            return _apply_linear(self.c_proj,
+                                 _apply_linear(self.c_fc, x, gelu=True))
         if os.environ.get("RLA_LT_MLP", "0") == "1":
             from ..ops.lt_mlp import fused_mlp as lt_fused
             return lt_fused(x, self.c_fc.weight, self.c_fc.bias,
@@ -246,7 +273,16 @@ class GPT2(nn.Module):
         the prefill, the pad tokens sit after the real ones, so no real
         token attends them, and their cache slots lie at or above the
         row's new length: they are overwritten before they are ever
-        attended."""
+        attended.
+
+        A model whose bf16 block weights were dropped
+        (``quantize_weights_fp8(drop_bf16=True)``) is for inference only:
+        in training mode the call raises ``RuntimeError``."""
+        if self.training and self.weights_dropped():
+            raise RuntimeError(
+                "the blocks' bf16 weights were dropped "
+                "(quantize_weights_fp8(drop_bf16=True)): the model runs in "
+                "eval mode only")
         if targets is None and doc_ids is None and \
                 self._fused_decode(idx, cache, extend):
             return self._decode_logits(idx, cache)[:, None], None
@@ -352,8 +388,19 @@ class GPT2(nn.Module):
         return (cache.k[i], cache.v[i], cache, cache.k_scale[i],
                 cache.v_scale[i])
 
+    def _block_linears(self):
+        for block in self.h:
+            yield from (block.attn.c_attn, block.attn.c_proj,
+                        block.mlp.c_fc, block.mlp.c_proj)
+
+    def weights_dropped(self) -> bool:
+        """Whether the blocks hold their linears as fp8 pairs only
+        (``quantize_weights_fp8`` drops all of them or none, so the first
+        block tells)."""
+        return len(self.h) > 0 and linear_dropped(self.h[0].attn.c_attn)
+
     @torch.no_grad()
-    def quantize_weights_fp8(self) -> "GPT2":
+    def quantize_weights_fp8(self, drop_bf16: bool = False) -> "GPT2":
         """Weight-only fp8 for the four linears of every block, on a bf16
         model in eval mode: each bf16 ``weight`` is overwritten with its
         dequantized e4m3 values (exact in bf16), and the codes and row
@@ -363,18 +410,34 @@ class GPT2(nn.Module):
         serves prefill, ``extend`` and every other path, which compute the
         same function, so the blocks' weight memory grows by half. The
         embeddings and the LM head stay bf16. Call it again after the
-        weights change; returns ``self``."""
+        weights change; returns ``self``.
+
+        ``drop_bf16=True`` frees the bf16 copies instead: each of those
+        ``weight`` parameters becomes an empty bf16 [0, K], the pair
+        becomes persistent buffers (a state dict still holds the model and
+        loads strictly into another dropped model), and every path applies
+        the linear through ``fp8_linear`` (ops/fp8_linear.py): ``N * K +
+        4 * N`` bytes per linear where bf16 takes ``2 * N * K``. The model
+        is then for inference only, and a second call raises
+        ``RuntimeError``, the bf16 values being gone."""
         from ..ops.skinny_linear import dequantize_weight, quantize_weight
         if self.training or self.wte.weight.dtype != torch.bfloat16:
             raise RuntimeError(
                 "quantize_weights_fp8 takes a bf16 model in eval mode")
-        for block in self.h:
-            for lin in (block.attn.c_attn, block.attn.c_proj,
-                        block.mlp.c_fc, block.mlp.c_proj):
-                q, scale = quantize_weight(lin.weight)
+        if self.weights_dropped():
+            raise RuntimeError(
+                "the blocks' bf16 weights were dropped: there is nothing "
+                "to quantize again")
+        for lin in self._block_linears():
+            q, scale = quantize_weight(lin.weight)
+            if drop_bf16:
+                lin.weight = nn.Parameter(
+                    lin.weight.new_empty(0, lin.weight.shape[1]),
+                    requires_grad=False)
+            else:
                 lin.weight.copy_(dequantize_weight(q, scale))
-                lin.register_buffer("weight_fp8", q, persistent=False)
-                lin.register_buffer("weight_scale", scale, persistent=False)
+            lin.register_buffer("weight_fp8", q, persistent=drop_bf16)
+            lin.register_buffer("weight_scale", scale, persistent=drop_bf16)
         return self
 
     def _fused_decode(self, idx, cache, extend=False) -> bool:
@@ -390,15 +453,25 @@ class GPT2(nn.Module):
             return False
         if idx.dim() != 2 or idx.shape[1] != 1 or not 1 <= idx.shape[0] <= 64:
             return False
-        from ..ops.skinny_linear import kernel_enabled, kernel_serves
+        from ..ops.skinny_linear import (fp8_enabled, kernel_enabled,
+                                         kernel_serves)
         w = self.wte.weight
         if w.dtype != torch.bfloat16 or not kernel_enabled():
             return False
         b0 = self.h[0]
+        # a dropped linear is judged by its fp8 matrix, the only one it
+        # has; with RLA_SKINNY_FP8=0 such a model takes the composed route
+        dropped = self.weights_dropped()
+        if dropped and not fp8_enabled():
+            return False
+
+        def mat(lin):
+            return lin.weight_fp8 if dropped else lin.weight
+
         return not w.is_cuda or (
-            kernel_serves(b0.attn.c_attn.weight, b0.ln_1.weight)
-            and kernel_serves(b0.mlp.c_fc.weight, b0.ln_2.weight)
-            and kernel_serves(b0.mlp.c_proj.weight)
+            kernel_serves(mat(b0.attn.c_attn), b0.ln_1.weight)
+            and kernel_serves(mat(b0.mlp.c_fc), b0.ln_2.weight)
+            and kernel_serves(mat(b0.mlp.c_proj))
             and kernel_serves(self.lm_head.weight, self.ln_f.weight))
 
     def _decode_logits(self, idx, cache):

@@ -25,6 +25,9 @@ Kernels (SURVEY.md N3/N6 hand-tuned halves):
 - linear layers of a decode step (at most 64 rows) as an MFMA weight
   stream with residual add, LayerNorm, bias and GELU fused, and a GPT-2
   block of a decode step from one host call (``skinny_linear.py``)
+- linear layers over fp8 (e4m3) weights at any row count: a tiled LDS MFMA
+  GEMM that converts each weight tile once, with the row scale, bias and
+  GELU in its epilogue (``fp8_linear.py``)
 """
 from __future__ import annotations
 

@@ -40,6 +40,7 @@ def build(verbose: bool = False) -> None:
                       os.path.join(_CSRC, "sample.hip"),
                       os.path.join(_CSRC, "spec_decode.hip"),
                       os.path.join(_CSRC, "skinny_linear.hip"),
+                      os.path.join(_CSRC, "fp8_linear.hip"),
                       os.path.join(_CSRC, "mfma_probe.hip")], []),
         ("_rccl_comm", [os.path.join(_CSRC, "rccl_comm.hip")],
          ["-L/opt/rocm/lib", "-lrccl"]),

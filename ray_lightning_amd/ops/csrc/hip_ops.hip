@@ -1148,6 +1148,16 @@ std::tuple<torch::Tensor, torch::Tensor> decode_layer_fp8_fwd(
     torch::Tensor mlp_proj_s, torch::Tensor mlp_proj_b, double eps,
     c10::optional<torch::Tensor> k_scale,
     c10::optional<torch::Tensor> v_scale);
+// linear layers over float8_e4m3fn weights at any row count: a tiled LDS
+// MFMA GEMM with the row scale, bias and GELU in its epilogue — defined in
+// fp8_linear.hip
+torch::Tensor fp8_linear_fwd(torch::Tensor x, torch::Tensor weight_fp8,
+                             torch::Tensor weight_scale,
+                             c10::optional<torch::Tensor> bias, bool gelu);
+torch::Tensor fp8_linear_fwd_at(torch::Tensor x, torch::Tensor weight_fp8,
+                                torch::Tensor weight_scale,
+                                c10::optional<torch::Tensor> bias, bool gelu,
+                                int64_t tile);
 // top-k / top-p / Philox token sampling with the decode loop's EOS and
 // output-write epilogue, one launch — defined in sample.hip
 torch::Tensor sample_fwd(torch::Tensor logits, torch::Tensor seeds,
@@ -1404,6 +1414,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_layer_fp8_fwd", &decode_layer_fp8_fwd,
         "decode_layer_fwd with float8_e4m3fn weights, each followed by its "
         "fp32 row scales; then k_scale / v_scale or None");
+  m.def("fp8_linear_fwd", &fp8_linear_fwd,
+        "y = act(x @ dequant(W)^T + bias) for bf16 x [M, K], float8_e4m3fn "
+        "W [N, K] and fp32 row scales [N], any M",
+        pybind11::arg("x"), pybind11::arg("weight_fp8"),
+        pybind11::arg("weight_scale"), pybind11::arg("bias"),
+        pybind11::arg("gelu"));
+  m.def("fp8_linear_fwd_at", &fp8_linear_fwd_at,
+        "fp8_linear_fwd at a tile of 64 or 128 (measurement, tests)");
   m.def("sample_fwd", &sample_fwd,
         "top-k / top-p / Philox sampling + EOS and output-write epilogue",
         pybind11::arg("logits"), pybind11::arg("seeds"),

@@ -243,16 +243,22 @@ def decode_layer(x: torch.Tensor, residual: Optional[torch.Tensor],
     if fp8_enabled() and all(
             getattr(m, "weight_fp8", None) is not None for m in linears):
         ws = [(m.weight_fp8, m.weight_scale) for m in linears]
+    elif any(m.weight.numel() == 0 for m in linears):
+        # GPT2.quantize_weights_fp8(drop_bf16=True) left the fp8 pair only
+        raise RuntimeError(
+            "decode_layer: the bf16 weights were dropped and RLA_SKINNY_FP8=0 "
+            "keeps the fp8 kernels off; apply the linears with fp8_linear")
     else:
         ws = [(m.weight, None) for m in linears]
     (aw, as_), (pw, ps), (fw, fs), (mw, ms) = ws
     # the one call reaches decode attention's kernel from C++, so that
-    # kernel's own gate (RLA_DECODE_ATTN) has to be on as well
-    if (_kernel_shape(x, c_attn.weight, ln1.weight) and kernel_enabled()
+    # kernel's own gate (RLA_DECODE_ATTN) has to be on as well. The shapes
+    # are read from the matrices chosen above: a dropped weight is empty.
+    if (_kernel_shape(x, aw, ln1.weight) and kernel_enabled()
             and _attn_kernel_enabled()
             and hs == 64 and k_cache.dtype == (
                 torch.bfloat16 if k_scale is None else FP8)
-            and c_fc.weight.shape[0] % 32 == 0
+            and fw.shape[0] % 32 == 0
             and ln2.weight.dtype == torch.float32
             and all(m.bias is not None for m in linears)):
         if as_ is not None:
